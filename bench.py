@@ -18,7 +18,12 @@ same-frame peak detection (histogram) -> EWA-Lanczos (Jinc) 2x polar upscale -> 
 (spline) + gamut mapping (perceptual 3D-LUT) -> BT.709 BT.1886 -> blue-noise dither to 10 bit
 -> 3840x2160 RGBA16. Nothing is skipped or cached between frames.
 
-The same line carries, per BASELINE.json config, one measured block under "rooflines"
+A plain run does only what `value` needs: set up, prime and warm up, time the K steps, print the
+line (its `roofline` is null). `--dump-outputs DIR` also writes what the last timed step rendered,
+as DIR/target_<i>.npy (see dump_outputs()). Everything below -- the per-pass and per-config
+measurements, the profiler passes, the companions and the CPU baseline -- runs only with `--full`.
+
+With --full the same line carries, per BASELINE.json config, one measured block under "rooflines"
 (frame time, dominant kernel, algorithmic GB/s, fraction of the 8 TB/s HBM peak AND of the
 157.3 TFLOP/s FP32 vector peak):
   bilinear_1080p_to_4k               configs[1]
@@ -805,6 +810,33 @@ def _run_timed(st, steps, warmup, sync=None, barrier=None):
     return elapsed
 
 
+DUMP_BYTES = 60 << 20       # --dump-outputs writes at most this much (float32)
+
+
+def dump_outputs(st, fps, out_dir):
+    """--dump-outputs: the targets the last timed step rendered, downloaded once the device is idle,
+    as DIR/target_<i>.npy (i: the target's index in the pool, so that the files do not depend on
+    how many frames the time-based priming rendered) in float32, normalised as the target's UNORM
+    format reads (code / 65535 for rgba16). A target that does not fit the budget is represented
+    by the same fixed sample of pixels in every file (rows of a (n, channels) array; flat pixel
+    indices drawn without replacement by np.random.default_rng(0), ascending)."""
+    os.makedirs(out_dir, exist_ok=True)
+    st.g.finish()
+    last = sorted({(st.i - 1 - k) % st.pool for k in range(min(fps, st.pool))})
+    budget = DUMP_BYTES // len(last)
+    idx = None
+    for i in last:
+        img = st.dsts[i].download()
+        h, w, nc = img.shape
+        if h * w * nc * 4 > budget:
+            if idx is None:
+                n = budget // (nc * 4)
+                idx = np.sort(np.random.default_rng(0).choice(h * w, n, replace=False))
+            img = img.reshape(h * w, nc)[idx]
+        unorm = np.float32(np.iinfo(img.dtype).max)
+        np.save(os.path.join(out_dir, f"target_{i}.npy"), img.astype(np.float32) / unorm)
+
+
 def config_block(device, workload, steps=60, warmup=8, trace=False):
     """One BASELINE config measured like the headline (single stream): frame rate + roofline."""
     (sw, sh), (dw, dh), _, _ = WORKLOADS[workload]
@@ -979,6 +1011,12 @@ def main():
     ap.add_argument("--frames-per-step", type=int, default=0,
                     help="frames of the pool a step renders (0 = the whole pool: one pass over the "
                          "batch of synthetic input; 1 = the single-frame steps of rounds 1-4)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-pass roofline, profiler "
+                         "passes, the other BASELINE configs, companions, CPU baseline (the --no-* "
+                         "options below select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step rendered to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-companions", action="store_true",
                     help="skip the per-config 'rooflines' blocks")
@@ -986,7 +1024,7 @@ def main():
     ap.add_argument("--no-concurrent", action="store_true",
                     help="skip the several-streams-on-one-GPU companion measurement")
     ap.add_argument("--bare", action="store_true",
-                    help="timed loop only (what the --pmc child processes run)")
+                    help="timed loop only, even with --full (what the --pmc child processes run)")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="(CPU) every rank joins a gloo group, all-reduces its rank, rank 0 prints "
                          "the sum: exercises the rank launcher without a GPU")
@@ -999,7 +1037,7 @@ def main():
         sys.exit(launcher_selftest())
     Stream.async_measure = bool(args.async_measure)
     if args.bare:
-        args.no_cpu_baseline = args.no_companions = args.no_traffic = args.no_concurrent = True
+        args.full = False
 
     import torch
 
@@ -1093,9 +1131,12 @@ def main():
             "mpixels_per_s_of_rank": [round(args.steps * fps * dw * dh / x / 1e6, 1) for x in own],
             "render_errors_of_rank": [int(e[3].item()) for e in every],
         }
+    if args.dump_outputs and rank == 0:
+        # (before anything below renders into the same targets)
+        dump_outputs(st, fps, args.dump_outputs)
 
     one_frame = None
-    if world == 1 and fps != 1:
+    if args.full and world == 1 and fps != 1:
         # the figure of rounds 1-4: K single-frame steps behind the same bracket (companion)
         dt1 = run_timed(st, args.steps, args.warmup, sync=torch.cuda.synchronize)
         one_frame = {"steps": args.steps, "warmup": args.warmup, "frames_per_step": 1,
@@ -1111,8 +1152,7 @@ def main():
         st.exchange = None
     if rank == 0:
         # the same K steps again, this time with a HIP event pair around every launch
-        roofline = None if args.bare else roofline_block(args.workload,
-                                                         measure_passes(st, args.steps))
+        roofline = roofline_block(args.workload, measure_passes(st, args.steps)) if args.full else None
         frames = args.steps * fps * world
         out = {
             "metric": baseline_metric(),
@@ -1153,7 +1193,7 @@ def main():
             out["one_frame_per_step"] = one_frame
     st.close()
 
-    if rank == 0 and world == 1 and not args.bare:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_traffic and roofline:
             t = measure_traffic(args.workload, roofline["kernel"].split(" ")[0])
             if t:

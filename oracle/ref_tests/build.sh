@@ -33,3 +33,12 @@ for t in ref_gpu_tests ref_bench; do
         -Wl,-rpath,'$ORIGIN/../../libplacebo_amd' -lm -lpthread
 done
 echo "built $OUT/ref_gpu_tests, $OUT/ref_bench"
+# the C-ABI examples of tests/c compiled against the REFERENCE's headers (search order: generated
+# config.h, the reference's headers, then include/ -- only hip.h is missing from the reference):
+# tests/test_gpu_c_abi.py runs them beside the same programs built against include/
+CABI="-std=c11 -O1 -D_GNU_SOURCE -Wall -Wno-deprecated-declarations -I$OUT/gen -I$REF/src/include -I$ROOT/include"
+for p in render_frame frame_stages gpu_contract pass_roundtrip; do
+    gcc $CABI "$ROOT/tests/c/$p.c" -o "$OUT/${p}_ref" -L"$ROOT/libplacebo_amd" -l:libplacebo_hip.so \
+        -Wl,-rpath,'$ORIGIN/../../libplacebo_amd' -lm
+done
+echo "built the tests/c programs against the reference's headers into $OUT"

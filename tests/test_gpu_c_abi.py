@@ -1,9 +1,10 @@
 """The drop-in boundary exercised from C.
 
-tests/c/render_frame.c is compiled twice (tests/c/Makefile, run by __graft_entry__.build()):
-against include/ and against the REFERENCE's own headers (only <libplacebo/hip.h> comes from
-this repository), both linked against libplacebo_hip.so. Both must render the same frame,
-and that frame must equal the oracle's, bit for bit. The second binary is the proof that
+tests/c/render_frame.c is compiled twice by __graft_entry__.build(): against include/
+(tests/c/Makefile) and against the REFERENCE's own headers (oracle/ref_tests/build.sh, into
+oracle/_ref/; only <libplacebo/hip.h> comes from this repository), both linked against
+libplacebo_hip.so. Both must render the same frame, and that frame must equal the oracle's, bit
+for bit. The second binary is the proof that
 structs laid out by libplacebo's declarations are what this library reads."""
 import os
 import subprocess
@@ -17,10 +18,15 @@ pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BUILD = os.path.join(ROOT, "tests", "c", "build")
+REF_BUILD = os.path.join(ROOT, "oracle", "_ref")     # the *_ref programs
+
+
+def exe_path(binary):
+    return os.path.join(REF_BUILD if binary.endswith("_ref") else BUILD, binary)
 
 
 def run(binary, out, sw, sh):
-    r = subprocess.run([os.path.join(BUILD, binary), out, str(sw), str(sh)],
+    r = subprocess.run([exe_path(binary), out, str(sw), str(sh)],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     return r.stdout
@@ -67,7 +73,7 @@ def test_c_program_renders_through_the_c_abi(gpu, tmp_path):
     util.assert_polar_equal(got, ref, what=log)
 
     # and the binary built against libplacebo's own headers
-    if not os.path.exists(os.path.join(BUILD, "render_frame_ref")):
+    if not os.path.exists(exe_path("render_frame_ref")):
         pytest.skip("render_frame_ref was not built (reference headers absent at build time)")
     log2 = run("render_frame_ref", str(tmp_path / "ref.raw"), sw, sh)
     raw2 = np.fromfile(tmp_path / "ref.raw", np.uint16)
@@ -84,7 +90,7 @@ def test_gpu_api_contract_from_c(gpu, binary):
     pl_pass_create / pl_pass_run on a recorded shader (raster and compute flavour, reuse, the
     shader freed first) byte-identical to pl_dispatch_finish -- each compiled against this
     repository's headers and against the reference's"""
-    exe = os.path.join(BUILD, binary)
+    exe = exe_path(binary)
     if not os.path.exists(exe):
         if binary.endswith("_ref"):
             pytest.skip("built only where the reference's headers exist")
@@ -102,7 +108,7 @@ def test_round5_stages_from_c_against_both_header_sets(gpu, tmp_path):
     W, H = 64, 48
     outs = {}
     for which in ("ours", "ref"):
-        exe = os.path.join(BUILD, f"frame_stages_{which}")
+        exe = exe_path(f"frame_stages_{which}")
         if not os.path.exists(exe):
             if which == "ref":
                 pytest.skip("frame_stages_ref not built (reference headers absent at build time)")

@@ -11,7 +11,7 @@ build)
     ls -la build_ab/*.so ;;
 run)
     shift
-    one() { python bench.py "$@" --steps 300 --warmup 30 --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['ms_per_step'], r['kernel_us'], r['frac'], r['passes_us'])"; }
+    one() { python bench.py "$@" --steps 300 --warmup 30 --full --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print(d['ms_per_step'], r['kernel_us'], r['frac'], r['passes_us'])"; }
     # (A B B A A B: consecutive processes on a box can alternate between two timing modes)
     for v in A B B A A B; do
         if [ $v = A ]; then echo -n "A: "; one "$@"
