@@ -7,9 +7,8 @@
  * Field names, meanings, defaults AND LAYOUTS are the reference's: `struct pl_frame`,
  * `struct pl_render_params` etc. built against libplacebo's own headers can be passed in
  * unchanged (tests/test_abi_layout.py). Members that select features outside the hot-path
- * scope (hooks, ICC, overlays, film grain, deinterlacing, distortion,
- * blurred borders) are declared at their reference offsets and refused or ignored at run
- * time as documented on each member.
+ * scope (hooks, ICC, film grain) are declared at their reference offsets
+ * and refused or ignored at run time as documented on each member.
  * Images and targets may be packed, semi-planar or planar / subsampled.
  */
 #ifndef LIBPLACEBO_RENDERER_H_
@@ -64,7 +63,10 @@ enum pl_clear_mode {
     PL_CLEAR_COLOR = 0, // set to the background colour
     PL_CLEAR_TILES,     // blend against / fill with the two-colour tile pattern
     PL_CLEAR_SKIP,      // leave untouched
-    PL_CLEAR_BLUR,      // (unsupported: treated as PL_CLEAR_COLOR)
+    PL_CLEAR_BLUR,      // border only: a blurred, stretched copy of the image (blur_radius); the
+                        // blurred RGB is swizzled into every plane without colour encoding, so a
+                        // YCbCr target receives RGB values in its border (the reference's
+                        // behaviour). As a background it is treated as PL_CLEAR_COLOR.
     PL_CLEAR_MODE_COUNT,
 };
 
@@ -122,8 +124,8 @@ struct pl_render_params {
     float background_transparency;
     float tile_colors[2][3];
     int tile_size;
-    float blur_radius;
-    float corner_rounding;              // unsupported (ignored)
+    float blur_radius;                  // border = PL_CLEAR_BLUR; <= 0: the image itself, stretched
+    float corner_rounding;              // (0, 1]: corner radius / half the crop's shorter side
 
     bool skip_anti_aliasing;
     bool preserve_mixing_cache;

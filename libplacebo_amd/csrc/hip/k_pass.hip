@@ -1773,9 +1773,12 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
     // Dolby Vision ops exist in one variant of the generic kernel only: such a pass (the
     // renderer's decoding pass of a Dolby Vision frame) goes straight there, past every
     // specialised kernel, and is refused behind a sampler that has its own kernel
+    // (the corner-rounding op lives in the same variant and takes the same way: no specialised
+    // kernel carries it, so none may be handed a pass with it -- it would be dropped)
     bool dovi = false;
     for (int i = 0; i < pass->num_ops; i++)
-        dovi |= pass->ops[i].kind == PLH_OP_DOVI_RESHAPE || pass->ops[i].kind == PLH_OP_DOVI_LMS;
+        dovi |= pass->ops[i].kind == PLH_OP_DOVI_RESHAPE || pass->ops[i].kind == PLH_OP_DOVI_LMS ||
+                pass->ops[i].kind == PLH_OP_CORNER_ROUND;
     if (dovi) {
         for (int i = 0; i < pass->num_ops; i++) {
             if (pass->ops[i].kind == PLH_OP_PEAK_DETECT)

@@ -260,6 +260,12 @@ enum plh_op_kind {
     // PQ EOTF, f[0..8] = LMS -> RGB (row-major), PQ OETF; f[9..13] = 1/m2 c1 c2 c3 1/m1,
     // f[14], f[15] = m1, m2
     PLH_OP_DOVI_LMS,
+    // pl_render_params.corner_rounding (renderer.c:2615-2652): relpos = the pass's output rect
+    // mapped onto [-f[1], f[1]] x [-f[2], f[2]]; rd = |relpos| - (f[1], f[2]) + f[0];
+    // border = smoothstep(2, 0, length(max(rd, 0)) - f[0]); i0 = 0: a = border, 1: a *= border,
+    // 2: color *= border. Like the Dolby Vision ops only in the generic kernel's DOVI variant,
+    // which plh_launch_pass sends every pass that carries it to.
+    PLH_OP_CORNER_ROUND,
 };
 
 // pl_reshape_data as the reshaping stage reads it (pl_shader_dovi_reshape packs the same)
@@ -424,6 +430,21 @@ struct plh_errdiff_args {
     int32_t block_size, blocks; // one workgroup, `blocks` sequential steps
 };
 
+/* ---- blurred borders (k_blur.hip): one level of the pyramid of the reference's pass_blur,
+ * src/renderer.c:2345-2465, as the fragment shader over the whole of `dst` would compute it ---- */
+// pos   = plh_attr(pos, (out_scale * (xy + 0.5)))   (sh_bind of the whole of `src`)
+// down  = (4 t(pos) + t(pos - s) + t(pos + s) + t(pos - (s.x, -s.y)) + t(pos + (s.x, -s.y))) / 8
+// up    = (t(pos -+ (2 s.x, 0)) + t(pos -+ (0, 2 s.y)) + 2 t(pos + (+-s.x, +-s.y))) / 12
+// t = bilinear with MIRROR addressing; `step` = offset / (src w, h), as the reference's uniform
+struct plh_blur_args {
+    struct plh_view src, dst;
+    float pos[4][2];
+    float out_scale[2];         // 1 / (dst w, h)
+    float step[2];
+};
+#define PLH_BLUR_TILE 16        // outputs per workgroup side
+#define PLH_BLUR_LDS 2048       // texels of the staged input footprint (float4: 32 KiB)
+
 /* ---- overlays and blended stores (k_overlay.hip) -------------------------------- */
 // What the reference draws as textured quads through the rasteriser with fixed-function blending
 // (draw_overlays, src/renderer.c:811-1020; pl_dispatch_finish with blend_params): a list of
@@ -494,6 +515,8 @@ struct plh_lowpass2 {
 int plh_launch_lowpass2(plh_stream stream, const struct plh_lowpass2 *args);
 int plh_lowpass2_applies(const struct plh_lowpass2 *args);
 int plh_launch_errdiff(plh_stream stream, const struct plh_errdiff_args *args);
+// up = 0: a downscale pass, 1: an upscale pass
+int plh_launch_blur(plh_stream stream, const struct plh_blur_args *args, int up);
 // pass: s.src = the overlay texture, ops (split at num_pre_ops), dst = the target
 int plh_launch_overlay(plh_stream stream, const struct plh_pass *pass,
                        const struct plh_overlay_args *args);

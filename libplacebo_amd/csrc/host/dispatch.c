@@ -678,6 +678,58 @@ int plh_dispatch_lowpass2(pl_dispatch dp, pl_shader *pvert, pl_shader *phoriz, p
     return 1;
 }
 
+bool plh_dispatch_blur(pl_dispatch dp, pl_shader *psh, pl_tex src, pl_tex dst, float offset, bool up)
+{
+    pl_shader sh = *psh;
+    bool ok = false;
+    if (sh->failed || !src || !dst || !dst->params.storable) {
+        pl_msg(dp->log, PL_LOG_ERR, "Trying to dispatch a blur pass without a storable target");
+        goto done;
+    }
+    sh->kind = PLH_SHADER_BLUR;
+    struct plh_blur_args *a = &sh->blur;
+    plh_tex_view(src, &a->src);
+    plh_tex_view(dst, &a->dst);
+    // sh_bind of the whole of `src` (shaders.c) and the compute-emulated rasterisation of the
+    // whole of `dst` (plh_pass_execute), as a pl_dispatch_finish of the reference's pass would set them
+    const float sx = 1.0 / src->params.w, sy = 1.0 / src->params.h;
+    a->pos[0][0] = a->pos[2][0] = 0.0f;
+    a->pos[1][0] = a->pos[3][0] = sx * (float) src->params.w;
+    a->pos[0][1] = a->pos[1][1] = 0.0f;
+    a->pos[2][1] = a->pos[3][1] = sy * (float) src->params.h;
+    a->out_scale[0] = 1.0 / dst->params.w;
+    a->out_scale[1] = 1.0 / dst->params.h;
+    // (${float: offset / w}: a float quotient)
+    a->step[0] = offset / src->params.w;
+    a->step[1] = offset / src->params.h;
+
+    pl_gpu gpu = dp->gpu;
+    struct pass_timing *timing = get_timing(dp, sh);
+    pl_timer timer = timing ? timing->timer : NULL;
+    (void) plh_tex_order(gpu, 0, src, dst);
+    if (timer)
+        plh_timer_begin(gpu, timer, 0);
+    plh_event stop = plh_gpu_fence_for_launch(gpu, 0, src);
+    plh_launch_offer_stop(stop);
+    const int err = plh_launch_blur(plh_gpu_stream_n(gpu, 0), a, up);
+    const bool taken = plh_launch_stop_taken() && !err;
+    if (timer)
+        plh_timer_end(gpu, timer, 0);
+    if (stop)
+        plh_gpu_fence_launched(gpu, 0, taken);
+    if (err) {
+        pl_msg(dp->log, PL_LOG_ERR, "Failed launching pass '%s': %s", sh_description(sh),
+               plh_strerror(err));
+        goto done;
+    }
+    drain_timing(dp, timing);
+    ok = true;
+
+done:
+    pl_dispatch_abort(dp, psh);
+    return ok;
+}
+
 size_t pl_dispatch_save(pl_dispatch dp, uint8_t *out)
 {
     return pl_cache_save(plh_gpu_cache(dp->gpu), out, out ? SIZE_MAX : 0);

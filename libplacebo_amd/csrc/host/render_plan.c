@@ -522,6 +522,48 @@ bool rp_wants_feature_map(const struct rp_caps *caps, const struct pl_render_par
 }
 
 /* ======================================================================================== */
+/* blurred border: :2345-2465 (pass_blur), :2596-2613                                        */
+
+bool rp_wants_blur(const struct pl_render_params *params, const struct pl_frame *target)
+{
+    const enum pl_clear_mode border = params->skip_target_clearing ? PL_CLEAR_SKIP : params->border;
+    return border == PL_CLEAR_BLUR && pl_frame_is_cropped(target);
+}
+
+void rp_plan_blur(float radius, int w, int h, struct rp_blur_plan *out)
+{
+    memset(out, 0, sizeof(*out));
+    out->w[0] = w;
+    out->h[0] = h;
+    if (radius <= 0.0f || (w == 1 && h == 1))
+        return;
+
+    // (the reference's expressions and types, float throughout but for the `1.0 +`)
+    const float a_min = 1.0, a_max = 1.8;
+    int passes = ceilf(logf(1.0 + radius * radius / (a_max * a_max)) / logf(4.0f));
+    passes = PL_CLAMP(passes, 2, RP_MAX_BLUR_PASSES);
+    float offset = radius / sqrtf(powf(4, passes) - 1.0f);
+    if (offset < a_min && passes > 2)
+        offset = radius / sqrtf(powf(4, --passes) - 1.0f);
+    if (offset > a_max && passes < RP_MAX_BLUR_PASSES)
+        offset = radius / sqrtf(powf(4, ++passes) - 1.0f);
+
+    for (int i = 0; i < passes + 1; i++) {
+        out->w[i] = w;
+        out->h[i] = h;
+        if (w == 1 && h == 1) {
+            passes = i;
+            break;
+        }
+        w = PL_MAX(w / 2, 1);
+        h = PL_MAX(h / 2, 1);
+    }
+    out->passes = passes;
+    out->offset = offset;
+    out->up = !(out->w[passes] == 1 && out->h[passes] == 1);
+}
+
+/* ======================================================================================== */
 /* output: :2586-2964 (pass_output_target)                                                    */
 
 void rp_plan_output(const struct pl_render_params *params, const struct pl_frame *target,
@@ -541,8 +583,10 @@ void rp_plan_output(const struct pl_render_params *params, const struct pl_frame
         out->background = PL_CLEAR_SKIP;
     if (params->skip_target_clearing)
         out->border = PL_CLEAR_SKIP;
-    // a blurred background / border is not implemented here: it shows the background colour
-    // (what the reference does when its blur pass is unavailable, :2500, PL_RENDER_ERR_BLUR)
+    // a blurred background is no valid mode (the reference's background switch has no case for
+    // it): the background colour. A blurred border stays a border to clear here; the executor
+    // draws it from the blurred image (rp_wants_blur) where that exists, else the background
+    // colour shows (:2500, PL_RENDER_ERR_BLUR)
     if (out->background == PL_CLEAR_BLUR)
         out->background = PL_CLEAR_COLOR;
     if (out->border == PL_CLEAR_BLUR)
@@ -773,6 +817,16 @@ void rp_summarise(const struct rp_caps *caps, const struct pl_frame *pimage,
         pl_color_transfer_name(target.color.transfer),
         img_color.transfer == PL_COLOR_TRC_LINEAR && image.repr.alpha != PL_ALPHA_PREMULTIPLIED
             ? " (prelinearized)" : "");
+
+    if (rp_wants_blur(params, &target) && caps->fbo[4] && !caps->blur_broken) {
+        struct rp_blur_plan bp;
+        rp_plan_blur(params->blur_radius, out_w, out_h, &bp);
+        say(s, "blur: radius %g passes %d offset %.9g levels", params->blur_radius, bp.passes,
+            bp.offset);
+        for (int i = 0; i <= bp.passes; i++)
+            say(s, " %dx%d", bp.w[i], bp.h[i]);
+        say(s, "%s\n", bp.up ? "" : " (no upscale)");
+    }
 
     struct rp_output_stage out;
     rp_plan_output(params, &target, &geo, comps, image.repr.alpha, &out);

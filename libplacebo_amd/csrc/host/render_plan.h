@@ -24,6 +24,7 @@ struct rp_caps {
     bool deband_broken;
     bool contrast_broken;
     bool errdiff_broken;
+    bool blur_broken;           // PL_RENDER_ERR_BLUR
 };
 
 /* ---- geometry ---- */
@@ -183,6 +184,26 @@ void rp_plan_output(const struct pl_render_params *params, const struct pl_frame
                     struct rp_output_stage *out);
 enum rp_dither rp_pick_dither(const struct rp_caps *caps, const struct pl_render_params *params,
                               int depth, int plane_h);
+
+/* ---- blurred border (pl_render_params.border = PL_CLEAR_BLUR) ---- */
+// The border of a cropped target is filled with a blurred, stretched copy of the finished image
+// (:2596-2613, clear_target :2491-2553): true if this frame asks for it (the target is cropped and
+// the border is neither skipped nor another mode). `background = PL_CLEAR_BLUR` is not a valid
+// background and stays a colour (rp_plan_output).
+bool rp_wants_blur(const struct pl_render_params *params, const struct pl_frame *target);
+
+#define RP_MAX_BLUR_PASSES 10
+// The pyramid of pass_blur (:2345-2465) for a w x h image: `passes` downscale passes from level 0
+// (the image itself) to level `passes`, each level half the previous (floor, at least 1), then as
+// many upscale passes back unless the last level is 1 x 1 (`up` false: that level is the border).
+// passes == 0: no blur at all (radius <= 0, a 1 x 1 image): the image is the border texture.
+struct rp_blur_plan {
+    int passes;
+    bool up;
+    float offset;           // tap distance in texels of the level a pass reads
+    int w[RP_MAX_BLUR_PASSES + 1], h[RP_MAX_BLUR_PASSES + 1];
+};
+void rp_plan_blur(float radius, int w, int h, struct rp_blur_plan *out);
 
 /* ---- human-readable plan (tests, PL_LOG_DEBUG) ---- */
 struct rp_summary {

@@ -117,6 +117,8 @@ void pl_renderer_flush_cache(pl_renderer rr)
         pl_tex_destroy(rr->gpu, &rr->fbos[i]);
     for (int i = 0; i < RR_MEASURE_FBOS; i++)
         pl_tex_destroy(rr->gpu, &rr->measure_fbo[i]);
+    for (int i = 0; i < RP_MAX_BLUR_PASSES + 1; i++)
+        pl_tex_destroy(rr->gpu, &rr->blur_levels[i]);
     rr->num_cached = rr->num_spare = rr->num_fbos = 0;
     pl_reset_detected_peak(rr->tone_map_state);
 }
@@ -701,6 +703,7 @@ bool plh_job_begin(struct frame_job *job, bool acquire_image)
     job->caps.deband_broken = rr->errors & PL_RENDER_ERR_DEBANDING;
     job->caps.contrast_broken = rr->errors & PL_RENDER_ERR_CONTRAST_RECOVERY;
     job->caps.errdiff_broken = rr->errors & PL_RENDER_ERR_ERROR_DIFFUSION;
+    job->caps.blur_broken = rr->errors & PL_RENDER_ERR_BLUR;
     choose_fbo_formats(job);
 
     pl_tex iref = job->image.planes[rp_reference_plane(&job->image)].texture,
@@ -1049,7 +1052,8 @@ static bool owns_workgroup_shape(const pl_shader sh)
     // ... and so do the Dolby Vision ops: one variant of the generic kernel, without the
     // measurement's workgroup state
     for (int i = 0; i < sh->pass.num_ops; i++) {
-        if (sh->pass.ops[i].kind == PLH_OP_DOVI_RESHAPE || sh->pass.ops[i].kind == PLH_OP_DOVI_LMS)
+        if (sh->pass.ops[i].kind == PLH_OP_DOVI_RESHAPE || sh->pass.ops[i].kind == PLH_OP_DOVI_LMS ||
+            sh->pass.ops[i].kind == PLH_OP_CORNER_ROUND)
             return true;
     }
     return false;
@@ -1605,6 +1609,160 @@ static bool distort_image(struct frame_job *job, struct work_image *img, struct 
     return true;
 }
 
+// The blurred border's pyramid over `src` (pass_blur, :2345-2465, on k_blur.hip): the texture the
+// border is drawn from, or NULL (PL_RENDER_ERR_BLUR raised)
+static pl_tex run_blur(struct frame_job *job, pl_tex src, int comps, float radius)
+{
+    pl_renderer rr = job->rr;
+    struct rp_blur_plan bp;
+    rp_plan_blur(radius, src->params.w, src->params.h, &bp);
+    if (!bp.passes)
+        return src;
+
+    pl_fmt fmt = job->caps.fbo[comps];
+    pl_tex lv[RP_MAX_BLUR_PASSES + 1] = { src };
+    for (int i = 0; i <= bp.passes; i++) {
+        const struct pl_tex_params want = {
+            .w = bp.w[i], .h = bp.h[i], .format = fmt,
+            .sampleable = true, .renderable = true, .storable = true,
+        };
+        if (!fmt || !(fmt->caps & PL_FMT_CAP_STORABLE) ||
+            !pl_tex_recreate(rr->gpu, &rr->blur_levels[i], &want))
+            goto error;
+        if (i)
+            lv[i] = rr->blur_levels[i];
+    }
+    // (level 0 is `src` for the downscale, a texture of its own for the last upscale)
+
+    for (int i = 0; i < bp.passes; i++) {
+        pl_shader sh = pl_dispatch_begin(rr->dp);
+        sh_describef(sh, "blur downscale pass %d", i + 1);
+        if (!plh_dispatch_blur(rr->dp, &sh, lv[i], lv[i + 1], bp.offset, false))
+            goto error;
+    }
+    if (!bp.up)
+        return lv[bp.passes];   // upscaling won't change the result
+
+    lv[0] = rr->blur_levels[0];
+    for (int i = bp.passes - 1; i >= 0; i--) {
+        pl_shader sh = pl_dispatch_begin(rr->dp);
+        sh_describef(sh, "blur upscale pass %d", bp.passes - i);
+        if (!plh_dispatch_blur(rr->dp, &sh, lv[i + 1], lv[i], bp.offset, true))
+            goto error;
+    }
+    return lv[0];
+
+error:
+    rr->errors |= PL_RENDER_ERR_BLUR;
+    return NULL;
+}
+
+// The border of a cropped target from the blurred image (clear_target, :2504-2547): every plane
+// whole, the image's rect stretched to the plane's aspect and sampled directly; then the target's
+// integer scale and the plane's swizzle -- no colour encoding: a YCbCr target receives the
+// swizzled RGB, as in the reference. `img_rect`: the image's rect when the blur was taken.
+static void draw_blur_border(struct frame_job *job, pl_tex border, pl_rect2df img_rect,
+                             const struct rp_output_stage *out)
+{
+    pl_renderer rr = job->rr;
+    const struct pl_render_params *params = job->params;
+    const struct pl_frame *target = &job->target;
+    for (int p = 0; p < target->num_planes; p++) {
+        const struct pl_plane *plane = &target->planes[p];
+        pl_shader sh = pl_dispatch_begin(rr->dp);
+        int ow = plane->texture->params.w, oh = plane->texture->params.h;
+        if (out->transposed) {
+            const int t = ow;
+            ow = oh;
+            oh = t;
+            sh->transpose = true;
+        }
+        pl_rect2df rect = img_rect;
+        pl_rect2df_aspect_set(&rect, (float) ow / oh, 0.0);
+        if (out->dst.x1 < out->dst.x0) {
+            const float t = rect.x0;
+            rect.x0 = rect.x1;
+            rect.x1 = t;
+        }
+        if (out->dst.y1 < out->dst.y0) {
+            const float t = rect.y0;
+            rect.y0 = rect.y1;
+            rect.y1 = t;
+        }
+        sh_describef(sh, "draw border");
+        pl_shader_sample_direct(sh, pl_sample_src( .tex = border, .rect = rect ));
+        plh_append_scale(sh, 1.0f / out->scale, !params->blend_params);
+        append_swizzle(sh, plane->components, plane->component_mapping, params->blend_params);
+        // (a border that fails to draw is logged by the dispatch, and the image is drawn all
+        // the same, as the reference's clear_target does)
+        pl_dispatch_finish(rr->dp, pl_dispatch_params(
+            .shader = &sh,
+            .target = plane->texture,
+            .blend_params = params->blend_params,
+        ));
+    }
+}
+
+// pl_render_params.corner_rounding (:2615-2652): the frame's corners fade out over two pixels
+// of a rounded rect the size of the target crop; the alpha this gives the image is what the
+// output's premultiply / background logic (rp_plan_output) then shows the background through.
+// The op exists in one variant of the generic kernel only (plh_device.h): a pending pass that
+// variant cannot run (a sampler with a kernel of its own, a measurement, frame mixing, the
+// tricubic LUT) is stored first, and the op goes onto a direct fetch of the result.
+static bool generic_can_run(const struct frame_job *job, const pl_shader sh)
+{
+    if (!sh || sh->kind != PLH_SHADER_PASS || sh->detect_peak || job->peak_pending ||
+        sh->pass.num_pre_ops)
+        return false;
+    const int t = sh->pass.s.type;
+    if (t >= PLH_SAMPLE_POLAR && t != PLH_SAMPLE_DISTORT)
+        return false;
+    for (int i = 0; i < sh->pass.num_ops; i++) {
+        const struct plh_op *op = &sh->pass.ops[i];
+        if (op->kind == PLH_OP_PEAK_DETECT || op->kind == PLH_OP_MIX_ADD ||
+            op->kind == PLH_OP_MIX_END || (op->kind == PLH_OP_GAMUT_LUT && op->f[3] != 0.0f))
+            return false;
+    }
+    return true;
+}
+
+static bool round_corners(struct frame_job *job, struct work_image *img)
+{
+    const struct pl_frame *target = &job->target;
+    const float out_w2 = fabsf(pl_rect_w(target->crop)) / 2.0f;
+    const float out_h2 = fabsf(pl_rect_h(target->crop)) / 2.0f;
+    const float radius = fminf(job->params->corner_rounding, 1.0f) * fminf(out_w2, out_h2);
+    // (without intermediates the pending pass is one of the simple samplers, which that variant
+    // runs too; a sampler it does not have refuses the launch, loudly)
+    if (img->rec && !generic_can_run(job, img->rec) && job->caps.fbo[4] &&
+        !plh_work_texture(job, img))
+        return false;
+    pl_shader sh = plh_work_shader(job, img);
+    struct plh_op *op = sh_op(sh, PLH_OP_CORNER_ROUND);
+    if (!op)
+        return false;
+    op->f[0] = radius;
+    op->f[1] = out_w2;
+    op->f[2] = out_h2;
+    switch (img->repr.alpha) {
+    case PL_ALPHA_UNKNOWN:
+    case PL_ALPHA_NONE:
+        op->i0 = 0;
+        img->repr.alpha = PL_ALPHA_INDEPENDENT;
+        img->comps = 4;
+        break;
+    case PL_ALPHA_INDEPENDENT:
+        op->i0 = 1;
+        break;
+    case PL_ALPHA_PREMULTIPLIED:
+    default:
+        op->i0 = 2;
+        break;
+    }
+    sh_listf(sh, "corner_round(radius %g, %g x %g, mode %d)\n", radius, out_w2, out_h2, op->i0);
+    return true;
+}
+
 bool plh_stage_output(struct frame_job *job)
 {
     pl_renderer rr = job->rr;
@@ -1612,6 +1770,34 @@ bool plh_stage_output(struct frame_job *job)
     const struct pl_frame *target = &job->target;
     struct work_image *img = &job->img;
     struct rp_geometry geo = job->geo;
+
+    // the blurred border is taken from the image at output size, before anything of the output
+    // stage (:2596-2613)
+    pl_tex border_tex = NULL;
+    if (rp_wants_blur(params, target) && !(rr->errors & PL_RENDER_ERR_BLUR)) {
+        // (into an intermediate of its own even where the image is a plain fetch of a texture, as
+        // the reference's img_tex does: the pyramid reads `comps` components, the rest as 0 0 0 1)
+        if (img->rec)
+            img->store_as = job->caps.fbo[img->comps];
+        pl_tex tex = job->caps.fbo[4] ? plh_work_texture(job, img) : NULL;
+        if (!tex) {
+            RR_LOG(rr, PL_LOG_ERR, "Output requires blurred borders, but FBOs are "
+                   "unavailable. This combination is unsupported.");
+            return false;
+        }
+        border_tex = run_blur(job, tex, img->comps, params->blur_radius);
+        if (!border_tex) {
+            RR_LOG(rr, PL_LOG_ERR, "Failed to generate blurred borders.");
+            return false;
+        }
+    }
+
+    // (distortion replaces img->rect; the border is drawn from the rect of the image it was
+    // blurred from, as the reference's img.rect, which its distortion leaves as it is)
+    const pl_rect2df border_rect = img->rect;
+
+    if (params->corner_rounding > 0.0f && !round_corners(job, img))
+        return false;
     if (params->distort_params && !distort_image(job, img, &geo))
         return false;
     pl_shader sh = plh_work_shader(job, img);
@@ -1666,8 +1852,11 @@ bool plh_stage_output(struct frame_job *job)
         img->h = t;
         sh->transpose = true;
     }
-    if (out.clear_border)
+    if (out.clear_border && border_tex) {
+        draw_blur_border(job, border_tex, border_rect, &out);
+    } else if (out.clear_border) {
         clear_planes(job, out.border);
+    }
 
     // a planar target samples the finished image once per plane
     pl_tex finished = NULL;

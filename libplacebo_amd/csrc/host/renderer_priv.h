@@ -64,6 +64,9 @@ struct pl_renderer_t {
     int num_cached;
     pl_tex spare[RR_MAX_CACHED_FRAMES];     // textures of evicted entries, for reuse
     int num_spare;
+    // the levels of the blurred border's pyramid (rp_plan_blur), level 0 the full size; kept
+    // apart from `fbos` so that a deep pyramid cannot starve the frame's other intermediates
+    pl_tex blur_levels[RP_MAX_BLUR_PASSES + 1];
 };
 
 // The image as it travels through a frame: either recorded-but-not-run (`rec`) or resident

@@ -32,6 +32,7 @@ struct pl_shader_obj_t {
 enum plh_shader_kind {
     PLH_SHADER_PASS = 0,        // sampler + colour ops -> plh_launch_pass
     PLH_SHADER_ERROR_DIFFUSION, // standalone compute (pl_dispatch_compute)
+    PLH_SHADER_BLUR,            // a level of the blurred border's pyramid (plh_dispatch_blur)
 };
 
 struct plh_errdiff_args;
@@ -70,6 +71,7 @@ struct pl_shader_t {
     uint64_t ticket;
 
     struct plh_errdiff_args *errdiff;
+    struct plh_blur_args blur;  // PLH_SHADER_BLUR
     // polar sampler state, for the launch-time phase-class setup (shader_sampling.c)
     void *polar_obj;
     // texture and rect bound by the sampling stage (sh_bind), for pass fusion
@@ -161,6 +163,9 @@ bool plh_dispatch_overlay(pl_dispatch dp, pl_shader *sh, pl_tex target,
 // the two recorded passes of a separable one-component downscale as one launch (dispatch.c):
 // 1 = done, 0 = declined (nothing consumed), -1 = failed
 int plh_dispatch_lowpass2(pl_dispatch dp, pl_shader *vert, pl_shader *horiz, pl_tex target);
+// one level of the blurred border's pyramid (k_blur.hip): `src` -> the whole of `dst`, taps `offset`
+// texels of `src` apart; `*sh` carries the pass's description only and is consumed
+bool plh_dispatch_blur(pl_dispatch dp, pl_shader *sh, pl_tex src, pl_tex dst, float offset, bool up);
 
 #define SH_GPU(sh) ((sh)->params.gpu)
 
