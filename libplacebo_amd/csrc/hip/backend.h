@@ -31,7 +31,6 @@ int plh_dev_count(void);
 const char *plh_strerror(int err);
 int plh_dev_open(int device, struct plh_dev_info *info);
 int plh_stream_create(int device, plh_stream *out);
-int plh_stream_create_masked(int device, int ncus, plh_stream *out);
 // the device that owns `s` (not the calling thread's current one) and, optionally, its CU count
 int plh_stream_device(plh_stream s, int *cus);
 // raise a kernel's dynamic-LDS limit on the stream's device, once per (kernel, device); `done` =

@@ -116,30 +116,6 @@ int plh_stream_create(int device, plh_stream *out)
     return 0;
 }
 
-// A stream whose kernels may only run on `ncus` of the device's compute units (0 or >= all of
-// them: an ordinary stream). The driver deals the bits of a CU mask out to the XCDs in turn -- bit
-// k is a CU of XCD k % 8 -- so the low `ncus` bits are ncus / 8 CUs on every XCD: the measuring
-// pass keeps every L2 and every memory channel, but its waves interleave with the scaler's on that
-// many CUs only instead of on all 256.
-int plh_stream_create_masked(int device, int ncus, plh_stream *out)
-{
-    CHK(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    CHK(hipGetDeviceProperties(&prop, device));
-    if (ncus <= 0 || ncus >= prop.multiProcessorCount)
-        return plh_stream_create(device, out);
-    uint32_t mask[32] = {0};
-    const int words = (prop.multiProcessorCount + 31) / 32;
-    if (words > 32)
-        return plh_stream_create(device, out);
-    for (int k = 0; k < ncus; k++)
-        mask[k / 32] |= 1u << (k % 32);
-    hipStream_t s;
-    CHK(hipExtStreamCreateWithCUMask(&s, (uint32_t) words, mask));
-    *out = (plh_stream) s;
-    return 0;
-}
-
 void plh_stream_destroy(plh_stream s)
 {
     if (s)

@@ -579,16 +579,11 @@ static bool deband_fast_ops(const plh_pass *pass)
 static bool deband_fast_applies(const plh_pass *pass)
 {
     const plh_sampler_args &s = pass->s;
-    const char *env = getenv("PL_HIP_DEBAND_FAST");
-    if (env && env[0] == '0')
+    if (!plh_switch(PLH_SW_DEBAND_FAST))
         return false;
-    const bool native = pass->width == s.src.w && pass->height == s.src.h &&
-        s.pos[0][0] == 0.0f && s.pos[0][1] == 0.0f && s.pos[3][0] == 1.0f && s.pos[3][1] == 1.0f &&
-        s.pos[1][0] == 1.0f && s.pos[1][1] == 0.0f && s.pos[2][0] == 0.0f && s.pos[2][1] == 1.0f;
-    return native && s.src.fmt == PLH_FMT_RGBA16 && pass->dst.fmt == PLH_FMT_RGBA16F &&
+    return plh_pass_covers_source(pass) && s.src.fmt == PLH_FMT_RGBA16 && pass->dst.fmt == PLH_FMT_RGBA16F &&
            s.address_mode == PLH_ADDRESS_CLAMP && (s.comp_mask & 7u) == 7u && !pass->transpose &&
-           pass->base_x == 0 && pass->base_y == 0 && pass->dir_x == 1 && pass->dir_y == 1 &&
-           pass->dst.w >= pass->width && pass->dst.h >= pass->height &&
+           plh_pass_plain_target(pass) &&
            (size_t) s.src.pitch * s.src.h < (1ull << 32) &&
            !pass->num_pre_ops && deband_fast_ops(pass);
 }
@@ -596,9 +591,8 @@ static bool deband_fast_applies(const plh_pass *pass)
 int plh_launch_deband(hipStream_t stream, const plh_pass *pass)
 {
     if (deband_fast_applies(pass)) {
-        const char *lds = getenv("PL_HIP_DEBAND_LDS");
         const plh_sampler_args &s = pass->s;
-        if (!(lds && lds[0] == '0') && s.db_lds && s.iterations >= 1 && s.db_radius * (float) s.iterations <= 16.0f) {
+        if (plh_switch(PLH_SW_DEBAND_LDS) && s.db_lds && s.iterations >= 1 && s.db_radius * (float) s.iterations <= 16.0f) {
             int cus = 256;
             (void) plh_stream_device((plh_stream) stream, &cus);
             const int tiles_x = (pass->width + DBL_TW - 1) / DBL_TW;

@@ -15,7 +15,6 @@
  * (two above, two below) are loaded once for both. The colour ops recorded behind the sampler run
  * through the interpreter, two pixels per lane.
  */
-#include <stdlib.h>
 
 #include "colorops.hiph"
 #include "backend.h"
@@ -515,10 +514,7 @@ static int deint_rows_variant(const plh_pass *p)
 {
     const plh_view &s = p->s.src, &d = p->dst;
     const plh_deint_args &a = p->deint;
-    static int off = -1;
-    if (off < 0)
-        off = getenv("PL_HIP_DEINT_ROWS") && !atoi(getenv("PL_HIP_DEINT_ROWS"));
-    if (off || p->num_ops || a.keep < 0 || s.fmt > PLH_FMT_RGBA16)
+    if (p->num_ops || a.keep < 0 || s.fmt > PLH_FMT_RGBA16)
         return 0;
     if (a.algo == PLH_DEINT_YADIF && s.fmt > PLH_FMT_RG16)
         return 0;   // (rgba16: a window of 13 dwords per row for half a pixel: the general kernel)

@@ -23,7 +23,6 @@
 #include "colorops.hiph"
 #include "samplers.hiph"
 #include "fastepi.hiph"
-#include <stdlib.h>
 
 #define ORTHO_BW 64
 #define ORTHO_BH 4
@@ -597,9 +596,7 @@ static bool ortho_fast_plane(int fmt)
 // -1: not eligible, else the epilogue variant
 static int ortho_fast_variant(plh_pass *pass)
 {
-    // PL_HIP_ORTHO_FAST=0: always the generic kernel (read per launch: tests switch kernels)
-    const char *e = getenv("PL_HIP_ORTHO_FAST");
-    const int enabled = e ? atoi(e) : 1;
+    const int enabled = plh_switch(PLH_SW_ORTHO_FAST);
     const plh_sampler_args &s = pass->s;
     const int n_axis = s.dir ? s.src.h : s.src.w;
     bool addr_ok = s.address_mode == PLH_ADDRESS_CLAMP;
@@ -971,11 +968,9 @@ static size_t lowpass2_lds(const plh_lowpass2 &a)
     return tile + (size_t) LP2_TH * a.cols_cap * 4;
 }
 
-// PL_HIP_LOWPASS_FUSED=0: the two passes
 extern "C" int plh_lowpass2_applies(const struct plh_lowpass2 *args)
 {
-    const char *env = getenv("PL_HIP_LOWPASS_FUSED");
-    if (env && env[0] == '0')
+    if (!plh_switch(PLH_SW_LOWPASS_FUSED))
         return 0;
     const plh_lowpass2 &a = *args;
     if (a.src.fmt != PLH_FMT_R16F || a.dst.fmt != PLH_FMT_R16F || a.n_v > 16 || a.n_h > 16 || a.n_v < 2 ||

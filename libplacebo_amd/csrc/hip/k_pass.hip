@@ -10,7 +10,6 @@
  * Memory-bound: every source texel and every target texel crosses HBM once.
  */
 #include <stdio.h>
-#include <stdlib.h>
 
 #include <string.h>
 #include <vector>
@@ -23,9 +22,6 @@
 #define PASS_BH 4
 #ifndef PASS_ITERS
 #define PASS_ITERS 1
-#endif
-#ifndef BF_DEFAULT_ITERS
-#define BF_DEFAULT_ITERS 1
 #endif
 
 // pl_shader_distort (sampling.c:1174-1215): the canvas position through the inverse transform,
@@ -855,15 +851,11 @@ void k_pass_merge(const plh_pass p_, const plh_merge m)
 static bool pass_merge_applies(plh_pass *pass, plh_merge *m)
 {
     const plh_sampler_args &s = pass->s;
-    const char *env = getenv("PL_HIP_PASS_NATIVE");
-    if (env && env[0] == '0')
+    if (!plh_switch(PLH_SW_PASS_NATIVE))
         return false;
-    const bool native = pass->width == s.src.w && pass->height == s.src.h &&
-        s.pos[0][0] == 0.0f && s.pos[0][1] == 0.0f && s.pos[3][0] == 1.0f && s.pos[3][1] == 1.0f &&
-        s.pos[1][0] == 1.0f && s.pos[1][1] == 0.0f && s.pos[2][0] == 0.0f && s.pos[2][1] == 1.0f;
-    if (!native || s.type != PLH_SAMPLE_NEAREST || s.address_mode != PLH_ADDRESS_CLAMP ||
-        pass->transpose || pass->num_pre_ops || pass->base_x || pass->base_y || pass->dir_x != 1 ||
-        pass->dir_y != 1 || pass->dst.w < pass->width || pass->dst.h < pass->height ||
+    if (!plh_pass_covers_source(pass) || s.type != PLH_SAMPLE_NEAREST ||
+        s.address_mode != PLH_ADDRESS_CLAMP || pass->transpose || pass->num_pre_ops ||
+        !plh_pass_plain_target(pass) ||
         (pass->dst.fmt != PLH_FMT_RGBA16 && pass->dst.fmt != PLH_FMT_RGBA16F))
         return false;
     const int n = pass->num_ops;
@@ -998,15 +990,11 @@ void k_pass_mix(const plh_pass p_, const plh_mixplan m)
 static bool pass_mix_applies(plh_pass *pass, plh_mixplan *m)
 {
     const plh_sampler_args &s = pass->s;
-    const char *env = getenv("PL_HIP_PASS_NATIVE");
-    if (env && env[0] == '0')
+    if (!plh_switch(PLH_SW_PASS_NATIVE))
         return false;
-    const bool native = pass->width == s.src.w && pass->height == s.src.h &&
-        s.pos[0][0] == 0.0f && s.pos[0][1] == 0.0f && s.pos[3][0] == 1.0f && s.pos[3][1] == 1.0f &&
-        s.pos[1][0] == 1.0f && s.pos[1][1] == 0.0f && s.pos[2][0] == 0.0f && s.pos[2][1] == 1.0f;
-    if (!native || s.type != PLH_SAMPLE_NEAREST || s.address_mode != PLH_ADDRESS_CLAMP ||
-        pass->transpose || pass->num_pre_ops || pass->base_x || pass->base_y || pass->dir_x != 1 ||
-        pass->dir_y != 1 || pass->dst.w < pass->width || pass->dst.h < pass->height ||
+    if (!plh_pass_covers_source(pass) || s.type != PLH_SAMPLE_NEAREST ||
+        s.address_mode != PLH_ADDRESS_CLAMP || pass->transpose || pass->num_pre_ops ||
+        !plh_pass_plain_target(pass) ||
         (pass->dst.fmt != PLH_FMT_RGBA16 && pass->dst.fmt != PLH_FMT_RGBA16F))
         return false;
     const int n = pass->num_ops;
@@ -1050,15 +1038,11 @@ static bool pass_mix_applies(plh_pass *pass, plh_mixplan *m)
 static bool pass_native_applies(const plh_pass *pass, bool features = false)
 {
     const plh_sampler_args &s = pass->s;
-    const char *env = getenv("PL_HIP_PASS_NATIVE");
-    if (env && env[0] == '0')
+    if (!plh_switch(PLH_SW_PASS_NATIVE))
         return false;
-    const bool native = pass->width == s.src.w && pass->height == s.src.h &&
-        s.pos[0][0] == 0.0f && s.pos[0][1] == 0.0f && s.pos[3][0] == 1.0f && s.pos[3][1] == 1.0f &&
-        s.pos[1][0] == 1.0f && s.pos[1][1] == 0.0f && s.pos[2][0] == 0.0f && s.pos[2][1] == 1.0f;
-    if (!native || s.type != PLH_SAMPLE_NEAREST || s.address_mode != PLH_ADDRESS_CLAMP ||
-        pass->transpose || pass->num_pre_ops || pass->base_x || pass->base_y || pass->dir_x != 1 ||
-        pass->dir_y != 1 || pass->dst.w < pass->width || pass->dst.h < pass->height ||
+    if (!plh_pass_covers_source(pass) || s.type != PLH_SAMPLE_NEAREST ||
+        s.address_mode != PLH_ADDRESS_CLAMP || pass->transpose || pass->num_pre_ops ||
+        !plh_pass_plain_target(pass) ||
         (s.src.fmt != PLH_FMT_RGBA16 && s.src.fmt != PLH_FMT_RGBA16F))
         return false;
     if (features)   // (k_pass_features: the one op into an r16hf plane)
@@ -1089,8 +1073,8 @@ static void launch_pass_native(hipStream_t stream, const plh_pass *pass)
 
 static bool nearest_fast_ok(plh_pass *pass)
 {
-    const char *e = getenv("PL_HIP_BILIN_ITERS");   // (0 = the generic kernel, as for bilinear)
-    if ((e && !atoi(e)) || pass->s.type != PLH_SAMPLE_NEAREST ||
+    // (0 = the generic kernel, as for bilinear)
+    if (!plh_switch(PLH_SW_BILIN_ITERS) || pass->s.type != PLH_SAMPLE_NEAREST ||
         pass->s.address_mode != PLH_ADDRESS_CLAMP || pass->num_pre_ops || pass->transpose ||
         (pass->s.src.fmt != PLH_FMT_RGBA16 && pass->s.src.fmt != PLH_FMT_RGBA16F))
         return false;
@@ -1101,9 +1085,7 @@ static bool nearest_fast_ok(plh_pass *pass)
 // 0: not eligible, else the number of cells per lane
 static int bilinear_fast_iters(plh_pass *pass)
 {
-    // PL_HIP_BILIN_ITERS=0 (off) | 1 | 2 | 4; read per launch so that tests can switch kernels
-    const char *e = getenv("PL_HIP_BILIN_ITERS");
-    const int iters_env = e ? atoi(e) : BF_DEFAULT_ITERS;
+    const int iters_env = plh_switch(PLH_SW_BILIN_ITERS);
     if (!iters_env || pass->s.type != PLH_SAMPLE_BILINEAR ||
         pass->s.address_mode != PLH_ADDRESS_CLAMP || pass->num_pre_ops || pass->transpose ||
         (pass->s.src.fmt != PLH_FMT_RGBA16 && pass->s.src.fmt != PLH_FMT_RGBA16F))
@@ -1380,7 +1362,7 @@ void k_bilinear_tab(const plh_pass p_, const float *colw_, const float *roww_, i
  * kept as the record of the experiment VERDICT r05 item 6 asked for.
  */
 #define BS_ROWS_DEFAULT 2      // (20.2 us; 4: 24.0, 8: 23.8 -- profiles/r06_12_strip_rows.txt)
-// (blockDim.y waves per workgroup, each with its own strip: 1 or 4 -- PL_HIP_BILIN_STRIP_WPG)
+// (blockDim.y waves per workgroup, each with its own strip; launched with one: four gained nothing)
 template <bool F16SRC, bool RGB, int BS_ROWS>
 __global__ __launch_bounds__(256)
 void k_bilinear_strip(const plh_pass p_, const float *colw_, const float *roww_, int b0x, int b0y)
@@ -1571,8 +1553,7 @@ static const bl_slot *bilinear_tables(hipStream_t stream, const plh_pass *pass)
     // (round 6: the tables are also what k_bilinear_strip runs on, PL_HIP_BILIN_STRIP=1 -- it lost as
     // well: 20.2 us in the trace with two cell rows per wave, 24.0 / 23.8 with four / eight, against
     // k_bilinear_fast's 19.0 on the same box, profiles/r06_11_strip_ab.txt, r06_12_strip_rows.txt)
-    const char *env = getenv("PL_HIP_BILIN_TABLES"), *strip = getenv("PL_HIP_BILIN_STRIP");
-    const bool want_tab = env && env[0] == '1', want_strip = strip && strip[0] == '1';
+    const bool want_tab = plh_switch(PLH_SW_BILIN_TABLES) == 1, want_strip = plh_switch(PLH_SW_BILIN_STRIP) == 1;
     if (!want_tab && !(want_strip && pass->s.src.w >= 2 && pass->dst.fmt == PLH_FMT_RGBA16))
         return nullptr;
     bl_key key = {};
@@ -1646,27 +1627,13 @@ static void launch_bilinear_tab(hipStream_t stream, const plh_pass *pass, const 
 {
     const int cells_w = (pass->width + pass->cell_padx + 1) / 2;
     const int cells_h = (pass->height + pass->cell_pady + 1) / 2;
-    const char *env = getenv("PL_HIP_BILIN_TABLES");
-    if (!(env && env[0] == '1')) {
-        // the strip kernel: a wave per 64 cell columns x ROWS cell rows
-        const char *renv = getenv("PL_HIP_BILIN_STRIP_ROWS");
-        const int rows = renv ? atoi(renv) : BS_ROWS_DEFAULT;
-        const char *wenv = getenv("PL_HIP_BILIN_STRIP_WPG");
-        const int wpg = wenv && atoi(wenv) == 4 ? 4 : 1;
-#define BS_LAUNCH(R) do { \
-            const dim3 sgrid((cells_w + 63) / 64, ((cells_h + R - 1) / R + wpg - 1) / wpg); \
-            if (pass->epi.has_alpha) \
-                PLH_LAUNCH_LAST((k_bilinear_strip<F16SRC, true, R>), sgrid, dim3(64, wpg), 0, stream, *pass, tab->colw, tab->roww, tab->b0x, tab->b0y); \
-            else \
-                PLH_LAUNCH_LAST((k_bilinear_strip<F16SRC, false, R>), sgrid, dim3(64, wpg), 0, stream, *pass, tab->colw, tab->roww, tab->b0x, tab->b0y); \
-        } while (0)
-        if (rows == 8)
-            BS_LAUNCH(8);
-        else if (rows == 2)
-            BS_LAUNCH(2);
+    if (plh_switch(PLH_SW_BILIN_TABLES) != 1) {
+        // the strip kernel: a wave per 64 cell columns x BS_ROWS_DEFAULT cell rows
+        const dim3 sgrid((cells_w + 63) / 64, (cells_h + BS_ROWS_DEFAULT - 1) / BS_ROWS_DEFAULT);
+        if (pass->epi.has_alpha)
+            PLH_LAUNCH_LAST((k_bilinear_strip<F16SRC, true, BS_ROWS_DEFAULT>), sgrid, dim3(64), 0, stream, *pass, tab->colw, tab->roww, tab->b0x, tab->b0y);
         else
-            BS_LAUNCH(4);
-#undef BS_LAUNCH
+            PLH_LAUNCH_LAST((k_bilinear_strip<F16SRC, false, BS_ROWS_DEFAULT>), sgrid, dim3(64), 0, stream, *pass, tab->colw, tab->roww, tab->b0x, tab->b0y);
         return;
     }
     const dim3 block(BF_BW, BF_BH), grid((cells_w + BF_BW - 1) / BF_BW, (cells_h + BF_BH - 1) / BF_BH);
@@ -1691,16 +1658,9 @@ static int plh_launch_generic(hipStream_t stream, const plh_pass *pass, bool cub
     const bool lite = plh_ops_lite(pass, 0, pass->num_ops);
     const bool simple = pass->s.type == PLH_SAMPLE_NONE || pass->s.type == PLH_SAMPLE_NEAREST ||
                         pass->s.type == PLH_SAMPLE_BILINEAR;
-    static int rows_override = -1;  // PL_HIP_PASS_ROWS=1|2 (profiling aid)
-    if (rows_override < 0) {
-        const char *e = getenv("PL_HIP_PASS_ROWS");
-        rows_override = e ? atoi(e) : 0;
-    }
     // 2x2 cells share the bilinear footprint; everything else prefers the lighter 2x1 cells
     // (measured: 4K colour map 193 -> 168 us, plane copy 20.4 -> 18.8 us)
     int ch = pass->s.type == PLH_SAMPLE_BILINEAR && lite ? 2 : 1;
-    if (rows_override == 1 || rows_override == 2)
-        ch = rows_override;
     bool mixing = false;
     for (int i = 0; i < pass->num_ops; i++)
         mixing |= pass->ops[i].kind == PLH_OP_MIX_ADD;
@@ -1744,10 +1704,7 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
     if (pass->width <= 0 || pass->height <= 0)
         return 0;
 
-    static int trace = -1;      // PL_HIP_PASS_TRACE=1: one line per launch on stderr
-    if (trace < 0)
-        trace = getenv("PL_HIP_PASS_TRACE") ? 1 : 0;
-    if (trace) {
+    if (plh_switch(PLH_SW_PASS_TRACE)) {
         fprintf(stderr, "[plh] pass %dx%d sampler=%d src.fmt=%d dst.fmt=%d transpose=%d pre=%d ops:",
                 pass->width, pass->height, pass->s.type, pass->s.src.fmt, pass->dst.fmt,
                 pass->transpose, pass->num_pre_ops);
@@ -1919,13 +1876,12 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
             // (profiles/r06_16_seg_ab.txt, r06_17_seg_ab.txt). At eight waves per SIMD this pass is
             // bound by the latency chain load -> tone gather -> gamut gathers -> store, not by
             // instruction issue; k_polar_mx at four waves per SIMD is, and gains 14 %.)
-            // the tone curve's table in LDS (PL_HIP_CHAIN_TONE_LDS=0: read where the op points)
+            // the tone curve's table in LDS where it fits
             size_t shmem = 0;
             local.chain.tone_lds = 0;
             {
-                const char *tenv = getenv("PL_HIP_CHAIN_TONE_LDS");
                 const int it = local.chain.tone;
-                if (!(tenv && tenv[0] == '0') && it >= 0 && local.ops[it].i0 >= 2 && local.ops[it].ptr) {
+                if (it >= 0 && local.ops[it].i0 >= 2 && local.ops[it].ptr) {
                     const int n = (int) local.ops[it].f[8] + 1;
                     if (n >= 2 && n <= PQSEG_TONE_MAX) {
                         local.chain.tone_lds = n;

@@ -757,15 +757,11 @@ void k_peak_tiles(const plh_pass p_)
 static bool peak_fast_applies(const plh_pass *pass)
 {
     const plh_sampler_args &s = pass->s;
-    const char *env = getenv("PL_HIP_PEAK_FAST");
-    if (env && env[0] == '0')
+    if (!plh_switch(PLH_SW_PEAK_FAST))
         return false;
-    const bool native = pass->width == s.src.w && pass->height == s.src.h &&
-        s.pos[0][0] == 0.0f && s.pos[0][1] == 0.0f && s.pos[3][0] == 1.0f && s.pos[3][1] == 1.0f &&
-        s.pos[1][0] == 1.0f && s.pos[1][1] == 0.0f && s.pos[2][0] == 0.0f && s.pos[2][1] == 1.0f;
+    const bool native = plh_pass_covers_source(pass);
     const bool target = pass->dst.ptr != NULL;
-    const bool plain_target = pass->base_x == 0 && pass->base_y == 0 && pass->dir_x == 1 && pass->dir_y == 1 &&
-                              pass->dst.w >= pass->width && pass->dst.h >= pass->height;
+    const bool plain_target = plh_pass_plain_target(pass);
     // PEAK_DETECT [LINEARIZE] FEATURES into the r16hf feature plane (STORE = 2)
     if (native && s.type == PLH_SAMPLE_NEAREST && s.scale == 1.0f &&
         (s.src.fmt == PLH_FMT_RGBA16 || s.src.fmt == PLH_FMT_RGBA16F) &&
@@ -777,9 +773,7 @@ static bool peak_fast_applies(const plh_pass *pass)
     return native && s.type == PLH_SAMPLE_NEAREST && s.scale == 1.0f &&
            (s.src.fmt == PLH_FMT_RGBA16 || s.src.fmt == PLH_FMT_RGBA16F) &&
            s.address_mode == PLH_ADDRESS_CLAMP && !pass->transpose && !pass->num_pre_ops &&
-           (!target || (pass->dst.fmt == PLH_FMT_RGBA16F && pass->base_x == 0 && pass->base_y == 0 &&
-                        pass->dir_x == 1 && pass->dir_y == 1 && pass->dst.w >= pass->width &&
-                        pass->dst.h >= pass->height)) &&
+           (!target || (pass->dst.fmt == PLH_FMT_RGBA16F && plain_target)) &&
            ((pass->num_ops == 1 && pass->ops[0].kind == PLH_OP_PEAK_DETECT) ||
             (pass->num_ops == 2 && pass->ops[0].kind == PLH_OP_PLANE_MAP && pass->ops[0].i2 &&
              pass->ops[0].i1 >= 1 && pass->ops[1].kind == PLH_OP_PEAK_DETECT));
@@ -858,23 +852,20 @@ int plh_launch_peak(hipStream_t stream, const plh_pass *pass)
             break;
         }
     }
-    const char *v2 = getenv("PL_HIP_PEAK_TILES");
     const int trc = pk_op < pass->num_ops ? pass->ops[pk_op].i0 : -1;
     const bool feat_target = pass->dst.ptr && pass->dst.fmt == PLH_FMT_R16F;
     // (the feature plane: PEAK_DETECT FEATURES of a linear image, or PEAK_DETECT LINEARIZE FEATURES of PQ)
     const bool feat_ok = !feat_target || pass->num_ops == 2 || pass->ops[1].i0 == TRC_PQ;
-    if (peak_fast_applies(pass) && !(v2 && v2[0] == '0') && feat_ok && pass->width >= 2 &&
+    if (peak_fast_applies(pass) && plh_switch(PLH_SW_PEAK_TILES) && feat_ok && pass->width >= 2 &&
         (trc == TRC_PQ || trc == TRC_LINEAR)) {
         // k_peak_tiles folds its own result (no k_peak_fold behind it)
         const bool f16 = pass->s.src.fmt == PLH_FMT_RGBA16F, store = pass->dst.ptr != NULL, pq = trc == TRC_PQ;
         const int per_slice = (tiles + PEAK_SLICES - 1) / PEAK_SLICES;
         // (two tiles per wave, at most 8 workgroups per CU. Measured beside the metric's scaler and
         // alone, 1080p and 4K, profiles/r05_06_peak_groups.txt: fewer, longer-lived workgroups suit
-        // the former, more the latter; this is the setting that loses neither)
-        const char *genv = getenv("PL_HIP_PEAK_GROUPS");
-        const int gmax = genv ? atoi(genv) : 170;
+        // the former, more the latter; a cap of 170 per slice is the setting that loses neither)
         int groups = (per_slice + 2 * PEAK_WAVES - 1) / (2 * PEAK_WAVES);
-        groups = groups < 1 ? 1 : groups > gmax ? gmax : groups;
+        groups = groups < 1 ? 1 : groups > 170 ? 170 : groups;
         const dim3 tgrid(PEAK_SLICES * groups);
 #define PEAK_TILES_GO(F, S, Q) PLH_LAUNCH_LAST((k_peak_tiles<F, S, Q>), tgrid, block, 0, stream, *pass)
         if (f16 && feat_target) { if (pq) PEAK_TILES_GO(true, 2, true); else PEAK_TILES_GO(true, 2, false); }

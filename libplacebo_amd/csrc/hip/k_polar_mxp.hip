@@ -451,8 +451,7 @@ void k_polar_mxp(const plh_pass p_)
 // Does the persistent kernel take this pass? (Else: k_polar_mx, which handles every shape.)
 bool plh_polar_mxp_applies(const plh_pass *pass)
 {
-    const char *env = getenv("PL_HIP_MX_PERSIST");
-    if (env && env[0] == '0')
+    if (!plh_switch(PLH_SW_MX_PERSIST))
         return false;
     const int fmt = pass->s.src.fmt;
     if ((pass->s.comp_mask & 0xf) != 0x7 || (fmt != PLH_FMT_RGBA16 && fmt != PLH_FMT_RGBA16F))
@@ -486,12 +485,8 @@ int plh_launch_polar_mxp(hipStream_t stream, const plh_pass *pass)
     int cus = 256;
     (void) plh_stream_device((plh_stream) stream, &cus);
     const int groups = min(tiles_x * tiles_y, 2 * cus);
-    const char *env = getenv("PL_HIP_MXP_STORE");
-    const int kind = env ? atoi(env) : (pass->nt_store ? MXP_STORE_DEFAULT : 0);
-    if (kind == 1)
-        launch_mxp<1>(stream, pass, groups, shmem);
-    else if (kind == 2)
-        launch_mxp<2>(stream, pass, groups, shmem);
+    if (pass->nt_store)
+        launch_mxp<MXP_STORE_DEFAULT>(stream, pass, groups, shmem);
     else
         launch_mxp<0>(stream, pass, groups, shmem);
     const hipError_t err = hipGetLastError();

@@ -14,6 +14,8 @@
 
 #include <stdint.h>
 
+#include "plh_switch.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -418,6 +420,23 @@ struct plh_pass {
     struct plh_deint_args deint;    // PLH_SAMPLE_DEINTERLACE
     struct plh_distort_args distort;    // PLH_SAMPLE_DISTORT
 };
+
+/* host side: two shapes the specialised kernels' `*_applies` tests share */
+// the pass covers its source 1:1: as large as it, `pos` = the unit square in the standard corner order
+static inline int plh_pass_covers_source(const struct plh_pass *pass)
+{
+    const struct plh_sampler_args *s = &pass->s;
+    return pass->width == s->src.w && pass->height == s->src.h &&
+        s->pos[0][0] == 0.0f && s->pos[0][1] == 0.0f && s->pos[3][0] == 1.0f && s->pos[3][1] == 1.0f &&
+        s->pos[1][0] == 1.0f && s->pos[1][1] == 0.0f && s->pos[2][0] == 0.0f && s->pos[2][1] == 1.0f;
+}
+
+// the target rect starts at the target's origin, runs forwards on both axes and fits
+static inline int plh_pass_plain_target(const struct plh_pass *pass)
+{
+    return pass->base_x == 0 && pass->base_y == 0 && pass->dir_x == 1 && pass->dir_y == 1 &&
+           pass->dst.w >= pass->width && pass->dst.h >= pass->height;
+}
 
 /* ---- error diffusion (k_errdiff.hip) ------------------------------------------ */
 struct plh_errdiff_args {

@@ -127,14 +127,11 @@ pl_hip pl_hip_create(pl_log log, const struct pl_hip_params *params)
 
     p->fns = &hip_fns;
     p->async_measure = params->async_measure && !params->stream;   // (own streams only)
-    // PL_HIP_ASYNC_MEASURE=0|1 overrides the parameter: lets a whole test suite or an unmodified
-    // application run with the option on
-    const char *async_env = getenv("PL_HIP_ASYNC_MEASURE");
-    if (async_env)
-        p->async_measure = atoi(async_env) && !params->stream;
-    // PL_HIP_MEASURE_CUS=n: the second stream is created with a CU mask of n units (n / 8 per XCD)
-    const char *cus_env = getenv("PL_HIP_MEASURE_CUS");
-    p->measure_cus = cus_env ? atoi(cus_env) : PLH_MEASURE_CUS_DEFAULT;
+    // (overrides the parameter: a whole test suite or an unmodified application with the option on)
+    const int async_sw = plh_switch(PLH_SW_ASYNC_MEASURE);
+    if (async_sw >= 0)
+        p->async_measure = async_sw && !params->stream;
+    plh_switch_report(log);
     struct pl_gpu_t *gpu = &p->gpu;
     gpu->log = log;
     gpu->glsl = (struct pl_glsl_version) {
@@ -275,7 +272,7 @@ plh_stream plh_gpu_stream_n(pl_gpu gpu, int on)
     if (!on || !p->async_measure)
         return p->stream;
     // (a greatest- or least-priority measuring stream changes nothing: profiles/r05_04_peak_prio.txt)
-    if (!p->aux && plh_stream_create_masked(p->device, p->measure_cus, &p->aux)) {
+    if (!p->aux && plh_stream_create(p->device, &p->aux)) {
         pl_msg(gpu->log, PL_LOG_WARN, "pl_hip: no second stream: async_measure disabled");
         p->async_measure = false;
         return p->stream;

@@ -64,8 +64,6 @@ struct plh_gpu_fns {
 #define PLH_STAGE_BYTES (64 * 1024)
 
 #define PLH_FENCES 16
-// compute units of the measuring stream's CU mask (0 = no mask); measured in profiles/r06_*
-#define PLH_MEASURE_CUS_DEFAULT 0
 
 struct gpu_priv {
     struct pl_gpu_t gpu;
@@ -78,7 +76,6 @@ struct gpu_priv {
     // pl_hip_params.async_measure: a second stream for the per-frame measurement pass
     // (index 1 in the functions below; index 0 is `stream`). Created on first use.
     bool async_measure;
-    int measure_cus;    // compute units the second stream may use (0: all; PL_HIP_MEASURE_CUS)
     plh_stream aux;
     bool aux_announced;
     // (gpu_hip.c "two streams") launches counted per stream, how far each is known to have got,

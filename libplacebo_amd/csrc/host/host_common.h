@@ -28,6 +28,9 @@ extern "C" {
 void pl_msg(pl_log log, enum pl_log_level lev, const char *fmt, ...)
     __attribute__((format(printf, 3, 4)));
 
+// warns, once per switch, of every PL_HIP_* switch (hip/plh_switch.h) whose value does not parse
+void plh_switch_report(pl_log log);
+
 #ifdef __cplusplus
 }
 #endif

@@ -502,8 +502,7 @@ static bool try_fused_polar(struct frame_job *job, pl_shader sh, const struct pl
                             pl_shader pre, int w, int h)
 {
     const struct pl_render_params *params = job->params;
-    const char *off = getenv("PL_HIP_NO_FUSION");
-    const int force = off && (off[0] == '0' || off[0] == '1') ? off[0] - '0' : -1;
+    const int force = plh_switch(PLH_SW_NO_FUSION);
     if (!pre || force == 1)
         return false;
     pl_fmt fmt = job->caps.fbo[job->img.comps];
@@ -1093,8 +1092,7 @@ static void measure_peak(struct frame_job *job)
             // measurement sees the colours before the FEATURES op replaces them.
             int mw, mh;
             pl_tex full = NULL;
-            const char *off = getenv("PL_HIP_FUSED_FEATURES");
-            if (!(off && off[0] == '0') && !job->features_full &&
+            if (plh_switch(PLH_SW_FUSED_FEATURES) && !job->features_full &&
                 rp_wants_feature_map(&job->caps, params, &img->color, &job->target.color,
                                      abs(pl_rect_w(job->geo.dst)), abs(pl_rect_h(job->geo.dst)), &mw, &mh))
                 full = borrow_fbo(job, img->w, img->h, NULL, 1);

@@ -1004,9 +1004,6 @@ static bool polar_mxr_build(pl_gpu gpu, pl_log log, struct sh_sampler_obj *obj,
 {
     const struct plh_sampler_args *s = &pass->s;
     const int W = pass->width, H = pass->height;
-    const char *env = getenv("PL_HIP_POLAR_MXR");
-    if (env && env[0] == '0')
-        return false;
     if (gpu->glsl.max_shmem_size < 64 * 1024 || s->bound > 4 || s->tile_fp32 ||
         s->address_mode != PLH_ADDRESS_CLAMP || pass->transpose || s->src.w < 2 || s->antiring > 0)
         return false;
@@ -1239,15 +1236,15 @@ static bool polar_pp_build(pl_gpu gpu, pl_log log, struct sh_sampler_obj *obj,
     const size_t texel = s->tile_fp32 ? 16 : 8;
     const size_t max_lds = 64 * 1024;   // >= 2 workgroups per CU
     int rows = n == 2 ? 3 : 4, tp = 0, ntc = 0;    // (measured: 3 beats 4 by ~2 % for 2x2 cells)
-    const char *env_rows = getenv("PL_HIP_PP_ROWS");     // profiling aid
-    if (env_rows && atoi(env_rows) > 0)
-        rows = PL_MIN(atoi(env_rows), 8);
+    const int rows_forced = plh_switch(PLH_SW_PP_ROWS);     // profiling aid
+    if (rows_forced > 0)
+        rows = PL_MIN(rows_forced, 8);
     rows = PL_MIN(rows, 64 / (POLAR_BH * n));   // the kernel stages <= 64 output rows of info
     // a small output (the chroma planes of 1080p video: 1920 x 1080 = 690 workgroups at 3 rows) does
     // not fill 256 CUs twice with such tiles, and the kernel lives on latency hiding: fewer rows
     // per workgroup until there are two rounds of them (NV12 1080p -> 4K, the chroma pass:
     // 37.5 -> 26.2 us, profiles/r04_49_pp_rows_small.txt)
-    if (!(env_rows && atoi(env_rows) > 0)) {
+    if (rows_forced <= 0) {
         while (rows > 1 && (size_t) ((W + POLAR_BW * n - 1) / (POLAR_BW * n)) *
                            (size_t) ((H + POLAR_BH * rows * n - 1) / (POLAR_BH * rows * n)) < 1024)
             rows--;
@@ -1256,8 +1253,6 @@ static bool polar_pp_build(pl_gpu gpu, pl_log log, struct sh_sampler_obj *obj,
     for (;; rows >>= 1) {
         free_axis_tiles(&tx);
         free_axis_tiles(&ty);
-        if (getenv("PL_HIP_PP_TRACE"))
-            pl_msg(log, PL_LOG_DEBUG, "polar phase classes: %dx%d classes, n=%d rows=%d", ncx, ncy, n, rows);
         if (!build_axis_tiles(&tx, idx, colbase, W, n, padx, POLAR_BW, s->bound) ||
             !build_axis_tiles(&ty, idy, rowbase, H, n, pady, POLAR_BH * rows, s->bound))
             goto done;
@@ -1420,8 +1415,7 @@ void plh_polar_pp_setup(pl_gpu gpu, pl_log log, void *polar_obj, struct plh_pass
     struct plh_sampler_args *s = &pass->s;
     s->pp = NULL;
     memset(&s->mx, 0, sizeof(s->mx));
-    const char *env = getenv("PL_HIP_POLAR_PER_PIXEL");
-    if (env && env[0] == '1')
+    if (plh_switch(PLH_SW_POLAR_PER_PIXEL))
         return;
     const uint32_t cm = s->comp_mask & 0xf;
     if (cm != 0x7 && cm != 0xf && cm != 0x1 && cm != 0x3)
@@ -1449,8 +1443,7 @@ void plh_polar_pp_setup(pl_gpu gpu, pl_log log, void *polar_obj, struct plh_pass
     s->pp_cells_w = obj->pp_host.cells_w;
     s->pp_cells_h = obj->pp_host.cells_h;
     s->pp_lds_weights = obj->pp_lds_weights;
-    const char *dbg = getenv("PL_HIP_PP_DEBUG");
-    s->pp_debug = dbg ? atoi(dbg) : 0;
+    s->pp_debug = plh_switch(PLH_SW_PP_DEBUG);
     s->tile_w = obj->pp_tile_w;
     s->tile_h = obj->pp_tile_h;
     s->tile_rows = obj->pp_rows;
@@ -1463,9 +1456,8 @@ void plh_polar_pp_setup(pl_gpu gpu, pl_log log, void *polar_obj, struct plh_pass
     // with the taps' products, which are small where the output is dark: measured <= 1 code at
     // 1080p -> 4K on white noise and on a dark field with isolated full-scale texels
     // (tests/test_gpu_default_kernels.py::test_matrix_pipe_behind_sigmoid_measured).
-    const char *mfma = getenv("PL_HIP_POLAR_MFMA");
     memset(&s->mx, 0, sizeof(s->mx));
-    if (obj->mx_host.enabled && !(mfma && mfma[0] == '0') && (cm == 0x7 || cm == 0xf) &&
+    if (obj->mx_host.enabled && plh_switch(PLH_SW_POLAR_MFMA) && (cm == 0x7 || cm == 0xf) &&
         !pass->transpose && s->address_mode == PLH_ADDRESS_CLAMP) {
         s->mx = obj->mx_host;
         if (!obj->mx_announced)

@@ -290,8 +290,7 @@ def test_whole_plane_kernel_equals_the_oracle(gpu, fmt, size, monkeypatch):
     """A whole unorm plane into a texture of its own format or of floats with the same components
     -- what the renderer asks for -- runs as k_deint_rows (a dword of a row pair per lane: bob,
     weave, bwdif) or k_deint_rows_yadif. Bit-exact against the oracle, rows that end inside a dword included, and equal
-    to the general kernel (PL_HIP_DEINT_ROWS=0 in a second process is not needed: the general
-    kernel is what every other test here runs, against the same oracle)."""
+    to the general kernel (which is what every other test here runs, against the same oracle)."""
     w, h = size
     arr = frames(w, h, fmt, seed=31)
     nc = arr[0].shape[2]
