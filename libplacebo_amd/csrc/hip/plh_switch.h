@@ -24,6 +24,7 @@ extern "C" {
     X(MAP_CHAIN,       "PL_HIP_MAP_CHAIN",        1, "0: colour-management ops walked by the interpreter instead of the straight-line chain") \
     X(PQ_SEGMENTS,     "PL_HIP_PQ_SEGMENTS",      1, "0: the chain's PQ pair in closed form instead of piecewise cubics in LDS") \
     X(PQ_SEG_COPIES,   "PL_HIP_PQ_SEG_COPIES",    1, "1 | 2 | 4 | 8 | 16 copies of every piece of those cubics in k_polar_mx's LDS") \
+    X(CHAIN_SHAPE,     "PL_HIP_CHAIN_SHAPE",      1, "0: k_polar_mx's generic chain instance always, instead of its shape-specialised one for HDR10 -> SDR passes (bit-identical)") \
     X(PASS_NATIVE,     "PL_HIP_PASS_NATIVE",      1, "0: 1:1 passes on k_pass_generic instead of k_pass_native / k_pass_chain / k_pass_merge / k_pass_mix") \
     X(BILIN_ITERS,     "PL_HIP_BILIN_ITERS",      1, "1 | 2 | 4 cells per lane of k_bilinear_fast; 0: k_pass_generic instead of it and of k_nearest_fast") \
     X(BILIN_TABLES,    "PL_HIP_BILIN_TABLES",     0, "1: the 2x bilinear upscale on k_bilinear_tab (per-axis tables) instead of k_bilinear_fast") \
