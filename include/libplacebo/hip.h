@@ -74,6 +74,17 @@ PL_API void *pl_hip_tex_ptr(pl_tex tex, size_t *out_row_pitch);
 // Device pointer of a buffer created by this backend.
 PL_API void *pl_hip_buf_ptr(pl_buf buf);
 
+// Kernels of the caller's own on a texture of this backend (a renderer hook, shaders/custom.h):
+// they go on `pl_hip->stream`, each after one call of this function per texture it touches --
+// the caller is about to queue work on that stream which reads (`write` false) or writes `tex`.
+// With `async_measure` the library runs some of its passes on a second stream and orders the
+// two by what each launch reads and writes; a kernel it did not launch is invisible to that
+// ordering. The call makes `pl_hip->stream` wait for whatever the second stream still has to do
+// with the texture, and notes the access so that later library passes are ordered behind it.
+// The counterpart of pl_vulkan_hold_ex / pl_vulkan_release_ex. On a pl_gpu with one stream it
+// does nothing.
+PL_API void pl_hip_tex_access(pl_gpu gpu, pl_tex tex, bool write);
+
 /* ---- multi-GPU: one scene rendered by several GPUs --------------------------
  * Streams are independent; the only state worth sharing is the HDR peak measurement when the
  * ranks render tiles or frames of ONE scene and must tone-map with one common peak. The

@@ -7,7 +7,7 @@
  * Field names, meanings, defaults AND LAYOUTS are the reference's: `struct pl_frame`,
  * `struct pl_render_params` etc. built against libplacebo's own headers can be passed in
  * unchanged (tests/test_abi_layout.py). Members that select features outside the hot-path
- * scope (hooks, ICC, film grain) are declared at their reference offsets
+ * scope (ICC, film grain) are declared at their reference offsets
  * and refused or ignored at run time as documented on each member.
  * Images and targets may be packed, semi-planar or planar / subsampled.
  */
@@ -19,6 +19,7 @@
 #include <libplacebo/filters.h>
 #include <libplacebo/gpu.h>
 #include <libplacebo/shaders/colorspace.h>
+#include <libplacebo/shaders/custom.h>
 #include <libplacebo/shaders/deinterlacing.h>
 #include <libplacebo/shaders/dithering.h>
 #include <libplacebo/shaders/film_grain.h>
@@ -50,7 +51,8 @@ enum pl_render_error {
 
 struct pl_render_errors {
     enum pl_render_error errors;
-    const uint64_t *disabled_hooks; // signatures; always NULL here (no hooks)
+    const uint64_t *disabled_hooks; // signatures of the hooks that failed and are skipped since;
+                                    // owned by the renderer, valid until its next call
     int num_disabled_hooks;
 };
 
@@ -113,7 +115,7 @@ struct pl_render_params {
     const struct pl_blend_params *blend_params;             // the frame is blended INTO the target
     const struct pl_deinterlace_params *deinterlace_params; // frames with a `field` are deinterlaced
     const struct pl_distort_params *distort_params;         // shaders/sampling.h: an affine map of the image
-    const struct pl_hook * const *hooks;                    // unsupported, must be NULL
+    const struct pl_hook * const *hooks;                    // shaders/custom.h: C callbacks at the renderer's stages
     int num_hooks;
     const struct pl_custom_lut *lut;    // applied between the image's and the target's colour
     enum pl_lut_type lut_type;          // space, see pl_lut_type

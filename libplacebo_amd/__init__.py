@@ -671,6 +671,16 @@ def render_params(preset="fast", **kw):
     return p
 
 
+def set_hooks(params, hooks):
+    """pl_render_params.hooks = pointers to `hooks` (capi.Hook structs, e.g. exported by a C
+    library: hooks are C callbacks); the array is kept alive on `params`."""
+    arr = (C.POINTER(capi.Hook) * max(len(hooks), 1))(*[C.pointer(h) for h in hooks])
+    params.hooks = C.cast(arr, C.c_void_p) if hooks else None
+    params.num_hooks = len(hooks)
+    params._hooks = (arr, list(hooks))
+    return params
+
+
 class Renderer:
     def __init__(self, gpu):
         self.gpu = gpu
@@ -690,6 +700,23 @@ class Renderer:
 
     def errors(self):
         return lib().pl_renderer_get_errors(self.rr).errors
+
+    def disabled_hooks(self):
+        """pl_render_errors.disabled_hooks as a list of signatures"""
+        e = lib().pl_renderer_get_errors(self.rr)
+        sigs = C.cast(e.disabled_hooks, C.POINTER(C.c_uint64))
+        return [sigs[i] for i in range(e.num_disabled_hooks)]
+
+    def reset_errors(self, errors=None, hooks=()):
+        """pl_renderer_reset_errors: everything (errors None), or the bits of `errors` -- with
+        PL_RENDER_ERR_HOOKS among them every disabled hook, or only the signatures in `hooks`"""
+        if errors is None:
+            lib().pl_renderer_reset_errors(self.rr, None)
+            return
+        sigs = (C.c_uint64 * max(len(hooks), 1))(*hooks)
+        e = capi.RenderErrors(errors=errors, num_disabled_hooks=len(hooks),
+                              disabled_hooks=C.cast(sigs, C.c_void_p) if hooks else None)
+        lib().pl_renderer_reset_errors(self.rr, C.byref(e))
 
     def destroy(self):
         if self.rr:

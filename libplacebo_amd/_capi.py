@@ -566,6 +566,60 @@ class RenderErrors(C.Structure):
                 ("num_disabled_hooks", C.c_int)]
 
 
+# ---- shaders/custom.h: renderer hooks (field layout only; hooks are written in C, because a
+# ctypes callback cannot return `struct pl_hook_res` by value) ----
+
+class CustomShader(C.Structure):
+    _fields_ = [("prelude", C.c_char_p), ("header", C.c_char_p), ("description", C.c_char_p),
+                ("body", C.c_char_p), ("input", C.c_int), ("output", C.c_int),
+                ("descriptors", C.c_void_p), ("num_descriptors", C.c_int),
+                ("variables", C.c_void_p), ("num_variables", C.c_int),
+                ("vertex_attribs", C.c_void_p), ("num_vertex_attribs", C.c_int),
+                ("constants", C.c_void_p), ("num_constants", C.c_int),
+                ("compute", C.c_bool), ("compute_shmem", C.c_size_t),
+                ("compute_group_size", C.c_int * 2), ("output_w", C.c_int), ("output_h", C.c_int)]
+
+
+class HookParams(C.Structure):
+    _fields_ = [("gpu", C.POINTER(Gpu)), ("dispatch", C.c_void_p), ("get_tex", C.c_void_p),
+                ("priv", C.c_void_p), ("stage", C.c_int), ("sh", C.c_void_p),
+                ("tex", C.POINTER(Tex)), ("rect", Rect2df), ("repr", ColorRepr),
+                ("color", ColorSpace), ("components", C.c_int),
+                ("orig_repr", C.POINTER(ColorRepr)), ("orig_color", C.POINTER(ColorSpace)),
+                ("src_rect", Rect2df), ("dst_rect", Rect2d)]
+
+
+class HookRes(C.Structure):
+    _fields_ = [("failed", C.c_bool), ("output", C.c_int), ("sh", C.c_void_p),
+                ("tex", C.POINTER(Tex)), ("repr", ColorRepr), ("color", ColorSpace),
+                ("components", C.c_int), ("rect", Rect2df)]
+
+
+class VarData(C.Union):
+    _fields_ = [("i", C.c_int), ("u", C.c_uint), ("f", C.c_float)]
+
+
+class HookPar(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("type", C.c_int), ("mode", C.c_int),
+                ("description", C.c_char_p), ("data", C.POINTER(VarData)), ("initial", VarData),
+                ("minimum", VarData), ("maximum", VarData), ("names", C.POINTER(C.c_char_p))]
+
+
+class Hook(C.Structure):
+    _fields_ = [("stages", C.c_int), ("input", C.c_int), ("priv", C.c_void_p),
+                ("parameters", C.POINTER(HookPar)), ("num_parameters", C.c_int),
+                ("reset", C.c_void_p), ("hook", C.c_void_p), ("signature", C.c_uint64)]
+
+
+# enum pl_hook_stage, in the order the renderer visits the stages
+HOOK_STAGES = ("RGB_INPUT", "LUMA_INPUT", "CHROMA_INPUT", "ALPHA_INPUT", "XYZ_INPUT",
+               "CHROMA_SCALED", "ALPHA_SCALED", "NATIVE", "RGB", "LINEAR", "SIGMOID",
+               "PRE_KERNEL", "POST_KERNEL", "SCALED", "PRE_OUTPUT", "OUTPUT")
+HOOK_STAGE = {name: 1 << i for i, name in enumerate(HOOK_STAGES)}
+HOOK_SIG_NONE, HOOK_SIG_COLOR, HOOK_SIG_TEX = 0, 1, 2
+RENDER_ERR_HOOKS = 1 << 10
+
+
 def declare(lib):
     """Attach argtypes/restypes."""
     P = C.POINTER
@@ -593,6 +647,10 @@ def declare(lib):
     fn("pl_hip_destroy", None, P(P(Hip)))
     fn("pl_hip_wrap", P(Tex), P(Gpu), P(HipWrapParams))
     fn("pl_hip_tex_ptr", vp, P(Tex), P(C.c_size_t))
+    fn("pl_hip_tex_access", None, P(Gpu), P(Tex), C.c_bool)
+    fn("pl_shader_custom", C.c_bool, vp, P(CustomShader))
+    fn("pl_mpv_user_shader_parse", P(Hook), P(Gpu), C.c_char_p, C.c_size_t)
+    fn("pl_mpv_user_shader_destroy", None, P(P(Hook)))
     fn("pl_find_named_fmt", P(Fmt), P(Gpu), C.c_char_p)
     fn("pl_find_fmt", P(Fmt), P(Gpu), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int)
     fn("pl_tex_create", P(Tex), P(Gpu), P(TexParams))
@@ -736,4 +794,11 @@ MIRRORS = {
     "struct pl_source_frame": SourceFrame, "struct pl_queue_params": QueueParams,
     "struct pl_render_params": RenderParams, "struct pl_dispatch_info": DispatchInfo,
     "struct pl_render_info": RenderInfo, "struct pl_render_errors": RenderErrors,
+}
+
+# the same for shaders/custom.h, against tests/golden/abi_layout_custom.json (tests/test_hooks_abi.py)
+MIRRORS_CUSTOM = {
+    "struct pl_custom_shader": CustomShader, "struct pl_hook_params": HookParams,
+    "struct pl_hook_res": HookRes, "union pl_var_data": VarData, "struct pl_hook_par": HookPar,
+    "struct pl_hook": Hook,
 }

@@ -547,6 +547,16 @@ void *pl_hip_tex_ptr(pl_tex tex, size_t *out_row_pitch)
     return t->ptr;
 }
 
+// A launch of the caller's own on the main stream, counted like one of the library's: the stream
+// waits for what the other one still does with `tex`, the texture remembers the number, and a
+// later pass on the other stream that depends on it marks the main stream's end at that time --
+// behind the caller's kernel, which is queued by then.
+void pl_hip_tex_access(pl_gpu gpu, pl_tex tex, bool write)
+{
+    if (gpu && tex)
+        plh_tex_order(gpu, 0, write ? NULL : tex, write ? tex : NULL);
+}
+
 static void hip_tex_clear_ex(pl_gpu gpu, pl_tex dst, const union pl_clear_color color)
 {
     struct plh_view v;

@@ -140,6 +140,23 @@ static uint64_t digest_params(const struct pl_render_params *p)
     MIX_POINTEE(p->lut, MIX_VALUE(&acc, p->lut->signature););
 #undef MIX_POINTEE
 
+    // Hooks are part of what a cached frame looks like (:3561-3569), member by member (no padding);
+    // one that only acts in the output stage runs once per output, on the mixed image, and leaves
+    // the cache alone
+    for (int i = 0; i < p->num_hooks; i++) {
+        const struct pl_hook *hook = p->hooks[i];
+        if (hook->stages == PL_HOOK_OUTPUT)
+            continue;
+        MIX_VALUE(&acc, hook->stages);
+        MIX_VALUE(&acc, hook->input);
+        MIX_VALUE(&acc, hook->priv);
+        MIX_VALUE(&acc, hook->parameters);
+        MIX_VALUE(&acc, hook->num_parameters);
+        MIX_VALUE(&acc, hook->reset);
+        MIX_VALUE(&acc, hook->hook);
+        MIX_VALUE(&acc, hook->signature);
+    }
+
     MIX_VALUE(&acc, p->lut_type);
     const uint8_t flags[] = {
         p->skip_anti_aliasing, p->disable_linear_scaling, p->disable_builtin_scalers,

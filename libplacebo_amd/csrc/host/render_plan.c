@@ -281,8 +281,14 @@ void rp_layout_image(const struct pl_frame *image, struct rp_image_layout *lay)
         }
     }
 
-    // The image proper lives on whole texels of the reference plane: drop the sub-texel offset
-    // (towards zero) and the sub-texel size mismatch, and remember both (:1810-1828)
+    rp_layout_snap(lay);
+}
+
+// The image proper lives on whole texels of the reference plane: drop the sub-texel offset
+// (towards zero) and the sub-texel size mismatch, and remember both (:1798-1815). Again after a
+// hook on a plane's input stage has changed a plane's rect.
+void rp_layout_snap(struct rp_image_layout *lay)
+{
     const pl_rect2df exact = lay->planes[lay->ref].rect;
     lay->grid.x0 = truncf(exact.x0);
     lay->grid.y0 = truncf(exact.y0);
@@ -411,6 +417,46 @@ struct rp_scaler rp_pick_scaler(const struct rp_caps *caps, const struct pl_rend
 }
 
 /* ======================================================================================== */
+/* hooks: which stages are asked for (:1036-1049, :1431-1445)                                 */
+
+uint64_t rp_hook_stages(const struct rp_caps *caps, const struct pl_render_params *params)
+{
+    uint64_t mask = 0;
+    if (!caps->fbo[4] || !params->hooks)
+        return 0;
+    for (int i = 0; i < params->num_hooks; i++)
+        mask |= (uint64_t) params->hooks[i]->stages;
+    return mask;
+}
+
+uint64_t rp_plane_hook_stage(enum rp_plane_role role, bool scaled)
+{
+    switch (role) {
+    case RP_PLANE_ALPHA:    return scaled ? PL_HOOK_ALPHA_SCALED : PL_HOOK_ALPHA_INPUT;
+    case RP_PLANE_CHROMA:   return scaled ? PL_HOOK_CHROMA_SCALED : PL_HOOK_CHROMA_INPUT;
+    case RP_PLANE_LUMA:     return scaled ? 0 : PL_HOOK_LUMA_INPUT;
+    case RP_PLANE_RGB:      return scaled ? 0 : PL_HOOK_RGB_INPUT;
+    case RP_PLANE_XYZ:      return scaled ? 0 : PL_HOOK_XYZ_INPUT;
+    case RP_PLANE_UNUSED:   break;
+    }
+    return 0;
+}
+
+const char *rp_hook_stage_name(uint64_t stage)
+{
+    static const char *const names[16] = {
+        "RGB_INPUT", "LUMA_INPUT", "CHROMA_INPUT", "ALPHA_INPUT", "XYZ_INPUT", "CHROMA_SCALED",
+        "ALPHA_SCALED", "NATIVE", "RGB", "LINEAR", "SIGMOID", "PRE_KERNEL", "POST_KERNEL",
+        "SCALED", "PRE_OUTPUT", "OUTPUT",
+    };
+    for (int i = 0; i < 16; i++) {
+        if (stage == (1ull << i))
+            return names[i];
+    }
+    return "?";
+}
+
+/* ======================================================================================== */
 /* main scaling stage: :1964-2087 (pass_scale_main)                                           */
 
 struct rp_scale_stage rp_plan_scale(const struct rp_caps *caps, const struct pl_render_params *params,
@@ -426,17 +472,26 @@ struct rp_scale_stage rp_plan_scale(const struct rp_caps *caps, const struct pl_
     // keeps it: measure on the smaller side
     st.peak_before = dir == RP_DIR_UP;
 
-    if (dir == RP_DIR_NONE && !fixed_size_input) {
+    // A hook on one of the stages around the scaler kernel wants the whole stage to exist, even
+    // where it would be skipped (:2004-2017); one on LINEAR / SIGMOID also wants that light
+    const uint64_t hooks = rp_hook_stages(caps, params);
+    const uint64_t kernel_hooks = PL_HOOK_PRE_KERNEL | PL_HOOK_POST_KERNEL,
+                   linear_hooks = PL_HOOK_LINEAR | PL_HOOK_SIGMOID;
+    const bool hooked = hooks & (kernel_hooks | linear_hooks);
+
+    if (dir == RP_DIR_NONE && !fixed_size_input && !hooked) {
         st.skip = true;
         return st;
     }
-    if (st.scaler.kind == RP_SCALER_BUILTIN && !fixed_size_input) {
+    if (st.scaler.kind == RP_SCALER_BUILTIN && !fixed_size_input && !hooked) {
         st.defer = true;
         return st;
     }
+    st.hooked = hooked && !fixed_size_input &&
+                (dir == RP_DIR_NONE || st.scaler.kind == RP_SCALER_BUILTIN);
 
-    st.sigmoid = dir == RP_DIR_UP && params->sigmoid_params;
-    st.linear = dir == RP_DIR_DOWN;
+    st.sigmoid = (dir == RP_DIR_UP && params->sigmoid_params) || (hooks & PL_HOOK_SIGMOID);
+    st.linear = dir == RP_DIR_DOWN || (hooks & linear_hooks);
 
     pl_fmt fbo = caps->fbo[comps];
     if (params->disable_linear_scaling || fbo->component_depth[0] < 16)
@@ -776,6 +831,19 @@ void rp_summarise(const struct rp_caps *caps, const struct pl_frame *pimage,
     const int comps = image.repr.alpha == PL_ALPHA_NONE ? 3 : 4;
     const int out_w = abs(pl_rect_w(geo.dst)), out_h = abs(pl_rect_h(geo.dst));
     struct pl_color_space img_color = image.color;
+
+    // the stages at which hooks are called, in the order they are visited: every plane's input
+    // stage, every plane's aligned stage, the merged image (:1779, :1873, :1917, :1959) ...
+    const uint64_t hooks = rp_hook_stages(caps, params);
+    uint64_t visit[4 * PL_MAX_PLANES + 8];
+    int num_visit = 0;
+    for (int scaled = 0; scaled < 2; scaled++) {
+        for (int i = 0; i < image.num_planes; i++)
+            visit[num_visit++] = rp_plane_hook_stage(lay.planes[i].role, scaled);
+    }
+    visit[num_visit++] = PL_HOOK_NATIVE;
+    visit[num_visit++] = PL_HOOK_RGB;
+
     if (caps->fbo[comps]) {
         const struct pl_sample_src req = {
             .components = comps, .new_w = out_w, .new_h = out_h,
@@ -795,19 +863,41 @@ void rp_summarise(const struct rp_caps *caps, const struct pl_frame *pimage,
         } else if (st.defer) {
             say(s, "scale: deferred to the output pass (%s)\n", scaler_name(&st.scaler));
         } else {
-            say(s, "scale: %s %s%s%s%s -> %dx%d\n", scaler_name(&st.scaler),
+            say(s, "scale: %s %s%s%s%s%s -> %dx%d\n", scaler_name(&st.scaler),
                 dir_name(st.scaler.dir), st.linear ? " linear" : "", st.sigmoid ? " sigmoid" : "",
                 st.scaler.kind == RP_SCALER_FILTER && !st.scaler.filter->polar &&
-                st.scaler.axis[0] && st.scaler.axis[1] ? " two-pass" : "", st.out_w, st.out_h);
+                st.scaler.axis[0] && st.scaler.axis[1] ? " two-pass" : "",
+                st.hooked ? " (kept for hooks)" : "", st.out_w, st.out_h);
             if (st.linear || st.sigmoid)
                 img_color.transfer = PL_COLOR_TRC_LINEAR;
+            // ... around the scaler kernel (:2054-2077) ...
+            if (st.linear || st.sigmoid)
+                visit[num_visit++] = PL_HOOK_LINEAR;
+            if (st.sigmoid)
+                visit[num_visit++] = PL_HOOK_SIGMOID;
+            visit[num_visit++] = PL_HOOK_PRE_KERNEL;
+            visit[num_visit++] = PL_HOOK_POST_KERNEL;
         }
+        visit[num_visit++] = PL_HOOK_SCALED;    // (:2085, also behind a skipped scaler)
         if (!why && !st.peak_before)
             say(s, "peak: measured after scaling\n");
         if (why && params->peak_detect_params)
             say(s, "peak: skipped (%s)\n", why);
     } else {
         say(s, "scale: no intermediate format, output pass samples directly\n");
+    }
+
+    // ... and in the output stage (:2703, :2795)
+    visit[num_visit++] = PL_HOOK_PRE_OUTPUT;
+    visit[num_visit++] = PL_HOOK_OUTPUT;
+    if (params->num_hooks) {
+        say(s, "hook stages:");
+        int said = 0;
+        for (int i = 0; i < num_visit; i++) {
+            if (visit[i] & hooks)
+                say(s, "%s%s", said++ ? " " : " ", rp_hook_stage_name(visit[i]));
+        }
+        say(s, "%s\n", said ? "" : caps->fbo[4] ? " none" : " none (no intermediate format)");
     }
 
     int mw, mh;

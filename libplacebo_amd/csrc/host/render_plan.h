@@ -81,6 +81,8 @@ struct rp_image_layout {
 };
 
 void rp_layout_image(const struct pl_frame *image, struct rp_image_layout *out);
+// grid / off / stretch from the reference plane's rect (again after a hook has changed a plane)
+void rp_layout_snap(struct rp_image_layout *lay);
 // sampling request that brings plane `i` onto the reference grid
 struct pl_sample_src rp_plane_request(const struct rp_image_layout *lay, int i);
 // true if that request is the identity (the plane already is the grid)
@@ -111,6 +113,15 @@ struct rp_scaler rp_pick_scaler(const struct rp_caps *caps, const struct pl_rend
                                 enum rp_usage usage, const struct pl_sample_src *req,
                                 pl_fmt src_format);
 
+/* ---- hooks (pl_render_params.hooks) ---- */
+// The stages at which some hook of `params` asks to be called: the union of the `stages` masks
+// (nothing else of a hook is looked at, and no callback is called). 0 where no hook can run:
+// without a four-component intermediate format none does (:1041).
+uint64_t rp_hook_stages(const struct rp_caps *caps, const struct pl_render_params *params);
+// the input / aligned stage of a plane of this role (0: none; :1431-1445)
+uint64_t rp_plane_hook_stage(enum rp_plane_role role, bool scaled);
+const char *rp_hook_stage_name(uint64_t stage);
+
 /* ---- main scaling stage ---- */
 struct rp_scale_stage {
     struct rp_scaler scaler;
@@ -120,6 +131,7 @@ struct rp_scale_stage {
     bool linear;            // scale in linear light
     bool sigmoid;           // ... and sigmoidized
     bool peak_before;       // measure the HDR peak before (else after) the scaler
+    bool hooked;            // runs only because a hook sits on LINEAR .. POST_KERNEL (:2004-2017)
     int out_w, out_h;
 };
 

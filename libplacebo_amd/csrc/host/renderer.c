@@ -19,8 +19,13 @@
  * into the polar kernel (the ops run on the source texels while they are staged, with the
  * rgba16hf rounding the intermediate image would have applied): same values, one pass less.
  *
- * Outside the scope of this backend: hooks (refused); ICC profiles, film grain
- * (ignored with an error bit / warning).
+ * pl_render_params.hooks (C callbacks, shaders/custom.h) are called at the reference's sixteen
+ * stages (plh_run_hooks, render_hooks.c). They add no fusion rule: a hook that leaves a texture
+ * leaves the image resident, one that appends ops leaves it recorded, and every decision below
+ * (try_fused_polar, is_pure_copy, the chain matcher in the dispatch) looks at the image as it finds it.
+ *
+ * Outside the scope of this backend: ICC profiles, film grain (ignored with an error
+ * bit / warning); hooks made from GLSL text (pl_mpv_user_shader_parse returns NULL).
  */
 #include <math.h>
 #include <stdlib.h>
@@ -143,18 +148,49 @@ void pl_renderer_destroy(pl_renderer *ptr)
     pl_shader_obj_destroy(&rr->dither_state);
     pl_dispatch_destroy(&rr->dp);
     free(rr->osd_parts);
+    free(rr->disabled_hooks);
     free(rr);
     *ptr = NULL;
 }
 
 struct pl_render_errors pl_renderer_get_errors(pl_renderer rr)
 {
-    return (struct pl_render_errors) { .errors = rr->errors };
+    return (struct pl_render_errors) {
+        .errors = rr->errors,
+        .disabled_hooks = rr->num_disabled_hooks ? rr->disabled_hooks : NULL,
+        .num_disabled_hooks = rr->num_disabled_hooks,
+    };
 }
 
+// :4203-4246. NULL: everything. Else the listed bits; with PL_RENDER_ERR_HOOKS among them, every
+// disabled hook (no signatures given) or the listed signatures only -- and the bit stays set for
+// as long as a hook remains disabled.
 void pl_renderer_reset_errors(pl_renderer rr, const struct pl_render_errors *errors)
 {
-    rr->errors = errors ? rr->errors & ~errors->errors : PL_RENDER_ERR_NONE;
+    if (!errors) {
+        rr->errors = PL_RENDER_ERR_NONE;
+        rr->num_disabled_hooks = 0;
+        return;
+    }
+    rr->errors &= ~errors->errors;
+    if (errors->errors & PL_RENDER_ERR_HOOKS) {
+        if (!errors->num_disabled_hooks) {
+            rr->num_disabled_hooks = 0;
+        } else if (errors->disabled_hooks) {
+            for (int i = 0; i < errors->num_disabled_hooks; i++) {
+                for (int j = 0; j < rr->num_disabled_hooks; j++) {
+                    if (rr->disabled_hooks[j] != errors->disabled_hooks[i])
+                        continue;
+                    memmove(&rr->disabled_hooks[j], &rr->disabled_hooks[j + 1],
+                            (rr->num_disabled_hooks - j - 1) * sizeof(rr->disabled_hooks[0]));
+                    rr->num_disabled_hooks--;
+                    break;
+                }
+            }
+        }
+    }
+    if (rr->num_disabled_hooks)
+        rr->errors |= PL_RENDER_ERR_HOOKS;
 }
 
 bool pl_renderer_get_hdr_metadata(pl_renderer rr, struct pl_hdr_metadata *metadata)
@@ -252,6 +288,11 @@ static pl_tex borrow_fbo(struct frame_job *job, int w, int h, pl_fmt fmt, int co
         return NULL;
     job->fbo_busy[pick] = true;
     return rr->fbos[pick];
+}
+
+pl_tex plh_borrow_fbo(struct frame_job *job, int w, int h, pl_fmt fmt, int comps)
+{
+    return borrow_fbo(job, w, h, fmt, comps);
 }
 
 // The intermediate of a pass that goes on the measurement stream (see renderer_priv.h)
@@ -560,6 +601,8 @@ static void forward_pass_info(void *priv, const struct pl_dispatch_info *dinfo)
 void plh_job_watch_passes(struct frame_job *job)
 {
     pl_dispatch_reset_frame(job->rr->dp);
+    if (job->params->num_hooks)
+        plh_reset_hooks(job->params);   // (:3370-3373)
     if (job->params->info_callback)
         pl_dispatch_callback(job->rr->dp, job, forward_pass_info);
     else
@@ -568,12 +611,18 @@ void plh_job_watch_passes(struct frame_job *job)
 
 bool plh_params_supported(pl_renderer rr, const struct pl_render_params *p)
 {
-    const char *what = p->num_hooks ? "hooks" : NULL;
-    if (!what)
-        return true;
-    RR_LOG(rr, PL_LOG_ERR, "pl_render_params.%s requests a stage this backend does not have "
-           "(outside the pl_render_image hot path, SURVEY.md 8)", what);
-    return false;
+    if (p->num_hooks < 0 || (p->num_hooks && !p->hooks)) {
+        RR_LOG(rr, PL_LOG_ERR, "pl_render_params.num_hooks = %d without a list of hooks",
+               p->num_hooks);
+        return false;
+    }
+    for (int i = 0; i < p->num_hooks; i++) {
+        if (!p->hooks[i] || !p->hooks[i]->hook) {
+            RR_LOG(rr, PL_LOG_ERR, "pl_render_params.hooks[%d] has no callback", i);
+            return false;
+        }
+    }
+    return true;
 }
 
 // things a frame may carry that are not rendered here: say so once, keep going
@@ -704,6 +753,7 @@ bool plh_job_begin(struct frame_job *job, bool acquire_image)
     job->caps.errdiff_broken = rr->errors & PL_RENDER_ERR_ERROR_DIFFUSION;
     job->caps.blur_broken = rr->errors & PL_RENDER_ERR_BLUR;
     choose_fbo_formats(job);
+    job->hook_stages = job->params->num_hooks ? rp_hook_stages(&job->caps, job->params) : 0;
 
     pl_tex iref = job->image.planes[rp_reference_plane(&job->image)].texture,
            tref = job->target.planes[rp_reference_plane(&job->target)].texture;
@@ -713,6 +763,7 @@ bool plh_job_begin(struct frame_job *job, bool acquire_image)
     job->image.crop = job->geo.src;
     job->target.crop = job->geo.dstf;
     rp_complete_frames(&job->image, &job->target);
+    job->ref_rect = job->image.crop;
     return true;
 }
 
@@ -901,11 +952,12 @@ bool plh_stage_read(struct frame_job *job)
     struct rp_image_layout lay;
     rp_layout_image(image, &lay);
 
-    // every plane: texture -> [deband] -> sampled onto the reference grid
+    // every plane: texture -> [deinterlace] -> [deband] -> [hooks of the plane's input stage] ...
     struct work_image pimg[PL_MAX_PLANES];
     float gain[PL_MAX_PLANES];
+    bool relaid = false;
     for (int i = 0; i < image->num_planes; i++) {
-        const struct rp_plane_layout *pl = &lay.planes[i];
+        struct rp_plane_layout *pl = &lay.planes[i];
         if (!pl->role)
             continue;
         pl_tex tex = image->planes[i].texture;
@@ -917,6 +969,28 @@ bool plh_stage_read(struct frame_job *job)
         };
         deinterlace_plane(job, &pimg[i], i);
         deband_plane(job, &pimg[i], pl->neutral);
+
+        // These stages are resizable: where a hook changed the plane's size or rect (a plane
+        // pre-scaler), the plane is what the hook left, and the alignment below follows (:1779-1785)
+        const int w = pimg[i].w, h = pimg[i].h;
+        const pl_rect2df rect = pimg[i].rect;
+        if (plh_run_hooks(job, &pimg[i], rp_plane_hook_stage(pl->role, false)) &&
+            (pimg[i].w != w || pimg[i].h != h || memcmp(&pimg[i].rect, &rect, sizeof(rect))))
+        {
+            pl->rect = pimg[i].rect;
+            pl->logical_w = pimg[i].w;
+            pl->logical_h = pimg[i].h;
+            relaid = true;
+        }
+    }
+    if (relaid)
+        rp_layout_snap(&lay);
+
+    // ... -> sampled onto the reference grid -> [hooks of the aligned plane's stage]
+    for (int i = 0; i < image->num_planes; i++) {
+        const struct rp_plane_layout *pl = &lay.planes[i];
+        if (!pl->role)
+            continue;
 
         struct pl_sample_src req = rp_plane_request(&lay, i);
         req.scale = pl_color_repr_normalize(&pimg[i].repr);
@@ -953,6 +1027,7 @@ bool plh_stage_read(struct frame_job *job)
             req.scale = 1.0;    // applied by the sampler
         }
         gain[i] = req.scale;
+        plh_run_hooks(job, &pimg[i], rp_plane_hook_stage(pl->role, true));
     }
 
     // the reference plane's recording becomes the pass; the others are fetched into it
@@ -1004,6 +1079,9 @@ bool plh_stage_read(struct frame_job *job)
         .fail_msg = ref->fail_msg, .fail_bit = ref->fail_bit, .fail_tex = ref->fail_tex,
     };
     struct work_image *img = &job->img;
+    job->ref_rect = img->rect;
+    if (plh_run_hooks(job, img, PL_HOOK_NATIVE))
+        sh = plh_work_shader(job, img);
 
     // Frame LUT (:1920-1946). NATIVE and CONVERSION see the raw samples (bit depth fixed up),
     // CONVERSION also does the decoding; NORMALIZED sees decoded RGB.
@@ -1037,7 +1115,10 @@ bool plh_stage_read(struct frame_job *job)
 
     // transparent regions must not bleed into opaque ones while filtering
     pl_shader_set_alpha(sh, &img->repr, PL_ALPHA_PREMULTIPLIED);
-    return !pl_shader_is_failed(sh);
+    if (pl_shader_is_failed(sh))
+        return false;
+    plh_run_hooks(job, img, PL_HOOK_RGB);
+    return true;
 }
 
 /* ---- HDR peak measurement ------------------------------------------------------------------- */
@@ -1178,12 +1259,17 @@ bool plh_stage_scale(struct frame_job *job)
         if (st.linear || st.sigmoid) {
             pl_shader_linearize(plh_work_shader(job, img), &img->color);
             img->color.transfer = PL_COLOR_TRC_LINEAR;
+            plh_run_hooks(job, img, PL_HOOK_LINEAR);
         }
-        if (st.sigmoid)
+        if (st.sigmoid) {
             pl_shader_sigmoidize(plh_work_shader(job, img), params->sigmoid_params);
+            plh_run_hooks(job, img, PL_HOOK_SIGMOID);
+        }
+        plh_run_hooks(job, img, PL_HOOK_PRE_KERNEL);
+        req.components = img->comps;
 
         // pass boundary: what is recorded so far either fuses into the polar kernel or lands
-        // in an intermediate image the scaler reads
+        // in an intermediate image the scaler reads (a hook that left a texture has decided)
         pl_shader sh = pl_dispatch_begin(rr->dp);
         if (img->rec && try_fused_polar(job, sh, &req, img->rec, img->w, img->h)) {
             pl_dispatch_abort(rr->dp, &img->rec);
@@ -1202,12 +1288,14 @@ bool plh_stage_scale(struct frame_job *job)
         img->w = st.out_w;
         img->h = st.out_h;
         img->rect = full;
+        plh_run_hooks(job, img, PL_HOOK_POST_KERNEL);
         if (st.sigmoid)
-            pl_shader_unsigmoidize(sh, params->sigmoid_params);
+            pl_shader_unsigmoidize(plh_work_shader(job, img), params->sigmoid_params);
     }
 
     if (!st.peak_before)
         measure_peak(job);
+    plh_run_hooks(job, img, PL_HOOK_SCALED);
     return true;
 }
 
@@ -1798,6 +1886,7 @@ bool plh_stage_output(struct frame_job *job)
         return false;
     if (params->distort_params && !distort_image(job, img, &geo))
         return false;
+    plh_run_hooks(job, img, PL_HOOK_PRE_OUTPUT);
     pl_shader sh = plh_work_shader(job, img);
 
     struct rp_output_stage out;
@@ -1850,6 +1939,10 @@ bool plh_stage_output(struct frame_job *job)
         img->h = t;
         sh->transpose = true;
     }
+    // (a hook that takes the image as a texture receives it rotated: the recording runs with its
+    // transposition, and what continues from the texture is upright)
+    if (plh_run_hooks(job, img, PL_HOOK_OUTPUT))
+        sh = plh_work_shader(job, img);
     if (out.clear_border && border_tex) {
         draw_blur_border(job, border_tex, border_rect, &out);
     } else if (out.clear_border) {
@@ -2062,7 +2155,7 @@ size_t plh_test_plan(const struct pl_frame *image, const struct pl_frame *target
                      char *out, size_t out_size)
 {
     struct rp_caps caps = { .max_shmem = max_shmem };
-    if (fbos) {
+    if (fbos && !(params && params->disable_fbos)) {
         caps.fbo[4] = caps.fbo[3] = plh_test_format("rgba16hf");
         caps.fbo[2] = plh_test_format("rg16hf");
         caps.fbo[1] = plh_test_format("r16hf");

@@ -67,6 +67,10 @@ struct pl_renderer_t {
     // the levels of the blurred border's pyramid (rp_plan_blur), level 0 the full size; kept
     // apart from `fbos` so that a deep pyramid cannot starve the frame's other intermediates
     pl_tex blur_levels[RP_MAX_BLUR_PASSES + 1];
+
+    // signatures of the hooks that failed (pl_render_errors.disabled_hooks): skipped until reset
+    uint64_t *disabled_hooks;
+    int num_disabled_hooks, cap_disabled_hooks;
 };
 
 // The image as it travels through a frame: either recorded-but-not-run (`rec`) or resident
@@ -108,6 +112,8 @@ struct frame_job {
     bool prev_acquired, next_acquired;
     bool target_borrowed;       // the target belongs to an enclosing job: neither acquire nor release
     struct pl_render_info info;
+    uint64_t hook_stages;       // rp_hook_stages: the stages some hook asks for (0: no hook runs)
+    pl_rect2df ref_rect;        // pl_hook_params.src_rect: the image crop, as the read stage left it
 };
 
 #define RR_LOG(rr, lev, ...) pl_msg((rr)->log, lev, __VA_ARGS__)
@@ -123,9 +129,18 @@ void plh_stage_colors(struct frame_job *job);
 bool plh_stage_output(struct frame_job *job);
 pl_shader plh_work_shader(struct frame_job *job, struct work_image *img);
 pl_tex plh_work_texture(struct frame_job *job, struct work_image *img);
+// an unused image of the renderer's pool, busy until the end of the job (fmt NULL: the
+// intermediate format for `comps` components)
+pl_tex plh_borrow_fbo(struct frame_job *job, int w, int h, pl_fmt fmt, int comps);
 // append a plain 1:1 fetch of another texture to `sh` as a colour op
 bool plh_append_plane_fetch(pl_shader sh, const pl_shader fetch, const struct pl_plane *plane);
 struct plh_op *plh_append_scale(pl_shader sh, float k, bool with_alpha);
+
+// render_hooks.c (reference pass_hook, src/renderer.c:1036-1181): call every enabled hook of
+// `stage` on `img`, which is replaced by what a hook returns. true if a hook was applied. A hook
+// that fails is disabled (by signature) and PL_RENDER_ERR_HOOKS raised; the image stays usable.
+bool plh_run_hooks(struct frame_job *job, struct work_image *img, uint64_t stage);
+void plh_reset_hooks(const struct pl_render_params *params);    // pl_hook.reset of every hook
 
 // render_overlay.c (reference draw_overlays, src/renderer.c:811-1020): `overlays` over `fbo`, which
 // holds `comps` components (`comp_map`: the plane's) of a frame in `color` / `repr`;

@@ -286,6 +286,8 @@ void sh_listf(pl_shader sh, const char *fmt, ...)
 
 struct plh_op *sh_op(pl_shader sh, int kind)
 {
+    if (sh->pass.num_ops >= PLH_MAX_OPS && sh->spill && !sh->failed)
+        sh->spill(sh->spill_priv, sh);
     if (sh->pass.num_ops >= PLH_MAX_OPS) {
         SH_FAIL(sh, "Too many colour stages in one shader (max %d)", PLH_MAX_OPS);
         return NULL;

@@ -84,6 +84,11 @@ struct pl_shader_t {
     // shader_color.c), given back when the shader is dispatched, reset or freed
     const void *scratch;
     pl_gpu scratch_gpu;
+    // Set while a renderer hook appends to this shader (render_hooks.c): called by sh_op when the
+    // op list is full, to run what is recorded into an intermediate image and leave `sh` as a
+    // plain fetch of it, so that the hook's ops are split over two passes instead of being lost
+    bool (*spill)(void *priv, pl_shader sh);
+    void *spill_priv;
 };
 
 // true if the only device memory the recorded pass reads is `src_tex` and the measurement's own

@@ -12,6 +12,11 @@ cross the C ABI to be layout-compatible with libplacebo's.
     tools/abi_probe.py ours            # table for include/
     tools/abi_probe.py ref             # table for /root/reference (needs oracle/_ref/gen)
     tools/abi_probe.py golden          # rewrite tests/golden/abi_layout.json from the reference
+    tools/abi_probe.py golden-custom   # the same for shaders/custom.h -> abi_layout_custom.json
+
+Headers listed in GROUPS have a table (and a golden file) of their own: every other command and
+function looks at the main set unless told otherwise, so that a header added later does not change
+the main table.
 
 Test infrastructure; the product does not use it.
 """
@@ -30,6 +35,13 @@ GOLDEN = os.path.join(ROOT, "tests", "golden", "abi_layout.json")
 
 # headers that only exist on this backend (no reference counterpart)
 OWN_HEADERS = {"libplacebo/hip.h"}
+
+# headers probed as a group of their own: group -> (headers, golden file)
+GROUPS = {
+    "custom": ({"libplacebo/shaders/custom.h"},
+               os.path.join(ROOT, "tests", "golden", "abi_layout_custom.json")),
+}
+GROUPED_HEADERS = set().union(*(g[0] for g in GROUPS.values()))
 
 
 def strip_comments(text):
@@ -96,9 +108,13 @@ def parse_header(path):
     return aggs
 
 
-def our_headers():
+def our_headers(group=None):
+    """The headers whose aggregates are probed: the main set, or those of `group`."""
     hs = sorted(glob.glob(os.path.join(OURS, "libplacebo", "**", "*.h"), recursive=True))
-    return [os.path.relpath(h, OURS) for h in hs]
+    hs = [os.path.relpath(h, OURS) for h in hs]
+    if group:
+        return [h for h in hs if h in GROUPS[group][0]]
+    return [h for h in hs if h not in GROUPED_HEADERS]
 
 
 def gen_program(headers, aggs):
@@ -116,12 +132,12 @@ def gen_program(headers, aggs):
     return "\n".join(lines) + "\n"
 
 
-def aggregates(which):
+def aggregates(which, group=None):
     """{(kind, name): [fields]} of every aggregate the chosen header set defines, restricted
     to the headers that exist on this backend."""
     root = OURS if which == "ours" else os.path.join(REF, "src", "include")
     out = {}
-    for h in our_headers():
+    for h in our_headers(group):
         if h in OWN_HEADERS and which != "ours":
             continue
         path = os.path.join(root, h)
@@ -142,14 +158,14 @@ def member_diff():
             only_ours)
 
 
-def run_probe(which, aggs=None):
+def run_probe(which, aggs=None, group=None):
     """Table for `which` in ("ours", "ref"). The member list comes from `aggs`
     ({(kind, name): fields}); default: the reference's members of the aggregates both
     header sets define (so a member include/ lacks is a compile error = a finding)."""
-    headers = [h for h in our_headers() if which == "ours" or h not in OWN_HEADERS]
+    headers = [h for h in our_headers(group) if which == "ours" or h not in OWN_HEADERS]
     if aggs is None:
-        ours = aggregates("ours")
-        aggs = {k: v for k, v in aggregates("ref").items() if k in ours}
+        ours = aggregates("ours", group)
+        aggs = {k: v for k, v in aggregates("ref", group).items() if k in ours}
     aggs = [(k[0], k[1], v) for k, v in aggs.items()]
     prog = gen_program(headers, aggs)
     if which == "ours":
@@ -178,6 +194,12 @@ def run_probe(which, aggs=None):
 
 def main():
     which = sys.argv[1] if len(sys.argv) > 1 else "ours"
+    if which.startswith("golden-"):
+        group = which[len("golden-"):]
+        t = run_probe("ref", group=group)
+        json.dump(t, open(GROUPS[group][1], "w"), indent=0, sort_keys=True)
+        print(f"wrote {GROUPS[group][1]}: {len(t)} entries")
+        return
     if which == "golden":
         t = run_probe("ref")
         json.dump(t, open(GOLDEN, "w"), indent=0, sort_keys=True)
