@@ -373,7 +373,7 @@ int plh_launch_polar(hipStream_t stream, const plh_pass *pass_in)
     const size_t px = pass->s.tile_fp32 ? sizeof(float4) : sizeof(uint2);
     const size_t shmem = 256 * sizeof(float2) + (size_t) pass->s.tile_w * pass->s.tile_h * px;
     if (shmem > 160 * 1024)
-        return -1000; // host picks tile sizes that fit; see shader_sampling.c
+        return -1000; // host picks tile sizes that fit; see shader_sampling.c, polar_tables.c
     if (pass->s.tile_fp32)
         return launch_mask<float>(stream, pass, grid, block, shmem);
     return launch_mask<__half>(stream, pass, grid, block, shmem);

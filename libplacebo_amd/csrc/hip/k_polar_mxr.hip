@@ -6,7 +6,7 @@
  * which are the same here. VERDICT r03 "missing 1". What is computed is the reference's polar
  * sampler (src/shaders/sampling.c:503-558 polar_sample, :587-912 pl_shader_sample_polar: every tap
  * within the radius weighted by the LUT at its distance, normalised by the weight sum) -- here with
- * the weights of each phase tabulated once per geometry by the host (shader_sampling.c:
+ * the weights of each phase tabulated once per geometry by the host (polar_mx_tables.c:
  * polar_mxr_build, from the same phase-class weights k_polar_pp uses).
  *
  * What changes with R. An axis has R phases; output X belongs to base index (X + sx) / R and phase

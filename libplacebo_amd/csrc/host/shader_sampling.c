@@ -21,7 +21,7 @@
 
 #include <libplacebo/shaders/sampling.h>
 
-#include "shaders_priv.h"
+#include "polar_priv.h"
 
 const struct pl_deband_params pl_deband_default_params = { PL_DEBAND_DEFAULTS };
 
@@ -182,45 +182,22 @@ bool pl_shader_sample_oversample(pl_shader sh, const struct pl_sample_src *src, 
 #define SCALER_LUT_SIZE     256
 #define SCALER_LUT_CUTOFF   1e-3f
 
-// Geometry a set of polar phase-class tables was built for (plh_polar_pp_setup)
-struct polar_pp_key {
-    float pos[4][2];
-    int src_w, src_h, width, height;
-    int bound, num_taps, fp32_tile;
-    float scale, radius;
-    uint64_t filter_gen;
-};
-
 struct sh_sampler_obj {
     pl_filter filter;
     pl_buf lut;         // polar: 256 {L[i], L[i+1]} pairs; ortho: rows
-    pl_buf taps;        // polar: packed tap list
     int num_taps;
     bool taps_gather;   // tap order the list was generated for
     pl_shader_obj pass2; // second ortho pass
-
-    // polar phase classes (k_polar_pp): one device blob holding struct plh_polar_pp
-    // and every table it points to
-    uint64_t filter_gen;            // bumped whenever lut/taps are regenerated
-    struct polar_pp_key pp_key;
-    int pp_state;                   // 0 = not built, 1 = usable, -1 = not applicable
-    pl_buf pp_blob;
-    struct plh_polar_pp pp_host;    // host copy (device pointers)
-    int pp_tile_w, pp_tile_h, pp_rows, pp_lds_weights;
-
-    // matrix-pipe variant of the same geometry (k_polar_mx): B fragments + tile origin
-    pl_buf mx_blob;
-    struct plh_polar_mx mx_host;    // .enabled = 0: geometry not eligible
-    bool mx_announced;
+    struct polar_tables polar;  // tap list and launch-time tables (polar_tables.c)
 };
 
 static void sh_sampler_uninit(pl_gpu gpu, void *ptr)
 {
     struct sh_sampler_obj *obj = ptr;
     pl_buf_destroy(gpu, &obj->lut);
-    pl_buf_destroy(gpu, &obj->taps);
-    pl_buf_destroy(gpu, &obj->pp_blob);
-    pl_buf_destroy(gpu, &obj->mx_blob);
+    pl_buf_destroy(gpu, &obj->polar.taps);
+    pl_buf_destroy(gpu, &obj->polar.pp_blob);
+    pl_buf_destroy(gpu, &obj->polar.mx_blob);
     pl_shader_obj_destroy(&obj->pass2);
     pl_filter_free(&obj->filter);
     memset(obj, 0, sizeof(*obj));
@@ -323,13 +300,6 @@ static int polar_taps_gather(uint32_t *taps, pl_filter filter, int bound, bool u
     return n;
 }
 
-// Output tile of the polar kernel (csrc/hip/k_polar.hip): 32 columns, 8 lanes
-// rows x `rows` rows per lane
-#ifndef POLAR_BW
-#define POLAR_BW 32
-#define POLAR_BH 8
-#endif
-
 static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
                          const struct pl_sample_filter_params *params, bool force_f16_tile);
 
@@ -396,7 +366,7 @@ static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
     const struct pl_glsl_version glsl = sh_glsl(sh);
     const bool gather_order = params->no_compute || !(filter->radius < 6.0);
 
-    if (update || !obj->lut || !obj->taps || obj->taps_gather != gather_order) {
+    if (update || !obj->lut || !obj->polar.taps || obj->taps_gather != gather_order) {
         // weight LUT as {L[i], L[min(i+1, 255)]} pairs: one ds_read_b64 per tap
         float pairs[2 * SCALER_LUT_SIZE];
         for (int i = 0; i < SCALER_LUT_SIZE; i++) {
@@ -411,17 +381,17 @@ static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
         obj->num_taps = gather_order ? polar_taps_gather(taps, filter, bound, use_ar, &glsl)
                                      : polar_taps_compute(taps, filter, bound, use_ar);
         obj->taps_gather = gather_order;
-        obj->filter_gen++;
+        obj->polar.filter_gen++;
 
         pl_buf_destroy(gpu, &obj->lut);
-        pl_buf_destroy(gpu, &obj->taps);
+        pl_buf_destroy(gpu, &obj->polar.taps);
         obj->lut = pl_buf_create(gpu, pl_buf_params(
             .size = sizeof(pairs), .storable = true, .initial_data = pairs));
-        obj->taps = pl_buf_create(gpu, pl_buf_params(
+        obj->polar.taps = pl_buf_create(gpu, pl_buf_params(
             .size = PL_MAX(obj->num_taps, 1) * sizeof(uint32_t), .storable = true,
             .initial_data = taps));
         free(taps);
-        if (!obj->lut || !obj->taps) {
+        if (!obj->lut || !obj->polar.taps) {
             SH_FAIL(sh, "Failed initializing polar LUT!");
             return false;
         }
@@ -458,7 +428,7 @@ static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
     struct plh_sampler_args *s = &sh->pass.s;
     s->type = PLH_SAMPLE_POLAR;
     s->lut = pl_hip_buf_ptr(obj->lut);
-    s->taps = pl_hip_buf_ptr(obj->taps);
+    s->taps = pl_hip_buf_ptr(obj->polar.taps);
     s->num_taps = obj->num_taps;
     s->bound = bound;
     s->radius = filter->radius;
@@ -470,7 +440,7 @@ static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
     s->tile_rows = rows;
     s->tile_fp32 = fp32_tile;
     s->pp = NULL;
-    sh->polar_obj = use_ar ? NULL : obj;    // anti-ringing needs per-pixel d, see k_polar
+    sh->polar_obj = use_ar ? NULL : &obj->polar;   // anti-ringing needs per-pixel d, see k_polar
     sh_hold(sh, *params->lut);
 
     sh_listf(sh, "sample_polar(filter=%s, radius=%f, radius_zero=%f, taps=%d (%s order), "
@@ -478,1171 +448,6 @@ static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
              PL_DEF(cfg.name, "custom"), filter->radius, filter->radius_zero, obj->num_taps,
              gather_order ? "gather" : "compute", tile_w, tile_h, fp32_tile ? "f32" : "f16",
              rows, cfg.antiring, info.scale, info.comp_mask);
-    return true;
-}
-
-
-/* ---- polar phase classes (device side: k_polar.hip, struct plh_polar_pp) ---------------- */
-
-static int cmp_u32(const void *a, const void *b)
-{
-    const uint32_t x = *(const uint32_t *) a, y = *(const uint32_t *) b;
-    return x < y ? -1 : x > y;
-}
-
-// distinct bit patterns of fc[0..n) -> sorted class values; ids[i] = class of element i
-static int classify_axis(const float *fc, int n, float *cls, uint16_t *ids, int max_cls)
-{
-    uint32_t *tmp = malloc(n * sizeof(uint32_t));
-    if (!tmp)
-        return -1;
-    memcpy(tmp, fc, n * sizeof(uint32_t));
-    qsort(tmp, n, sizeof(uint32_t), cmp_u32);
-    int nc = 0;
-    for (int i = 0; i < n; i++) {
-        if (i && tmp[i] == tmp[i - 1])
-            continue;
-        if (nc == max_cls) {
-            free(tmp);
-            return -1;
-        }
-        memcpy(&cls[nc++], &tmp[i], 4);
-    }
-    free(tmp);
-    for (int i = 0; i < n; i++) {
-        uint32_t key;
-        memcpy(&key, &fc[i], 4);
-        int lo = 0, hi = nc - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi) / 2;
-            uint32_t v;
-            memcpy(&v, &cls[mid], 4);
-            if (v < key)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        ids[i] = lo;
-    }
-    return nc;
-}
-
-// Can `n` consecutive outputs [n*c - pad, n*c - pad + n) always share a base texel?
-static bool cells_share_base(const int32_t *base, int len, int n, int pad)
-{
-    for (int c0 = -pad; c0 < len; c0 += n) {
-        int b = 0;
-        bool have = false;
-        for (int i = 0; i < n; i++) {
-            const int x = c0 + i;
-            if (x < 0 || x >= len)
-                continue;
-            if (have && base[x] != b)
-                return false;
-            b = base[x];
-            have = true;
-        }
-    }
-    return true;
-}
-
-struct axis_tiles {
-    int ntiles;
-    uint8_t *loc;       // [len]
-    uint16_t *list;     // [ntiles][PLH_PP_LMAX]
-    uint8_t *cnt;       // [ntiles]
-    int32_t *org;       // [ntiles]
-    int extent;         // LDS tile extent needed along this axis (texels)
-    int max_cnt;
-};
-
-// Split an axis of `len` outputs into tiles of `tile_cells` cells of `n` outputs
-static bool build_axis_tiles(struct axis_tiles *t, const uint16_t *ids, const int32_t *base,
-                             int len, int n, int pad, int tile_cells, int bound)
-{
-    const int cells = (len + pad + n - 1) / n;
-    t->ntiles = (cells + tile_cells - 1) / tile_cells;
-    t->loc = calloc(len, 1);
-    t->list = calloc((size_t) t->ntiles * PLH_PP_LMAX, sizeof(uint16_t));
-    t->cnt = calloc(t->ntiles, 1);
-    t->org = calloc(t->ntiles, sizeof(int32_t));
-    t->extent = 0;
-    t->max_cnt = 0;
-    if (!t->loc || !t->list || !t->cnt || !t->org)
-        return false;
-    for (int ti = 0; ti < t->ntiles; ti++) {
-        const int x0 = PL_MAX(ti * tile_cells * n - pad, 0);
-        const int x1 = PL_MIN((ti + 1) * tile_cells * n - pad, len);
-        uint16_t *list = t->list + (size_t) ti * PLH_PP_LMAX;
-        int cnt = 0, bmin = INT32_MAX, bmax = INT32_MIN;
-        for (int x = x0; x < x1; x++) {
-            int l = 0;
-            while (l < cnt && list[l] != ids[x])
-                l++;
-            if (l == cnt) {
-                if (cnt == PLH_PP_LMAX)
-                    return false;
-                list[cnt++] = ids[x];
-            }
-            t->loc[x] = l;
-            bmin = PL_MIN(bmin, base[x]);
-            bmax = PL_MAX(bmax, base[x]);
-        }
-        if (x1 <= x0) {
-            bmin = bmax = 0;
-            cnt = 1;
-        }
-        t->cnt[ti] = cnt;
-        t->max_cnt = PL_MAX(t->max_cnt, cnt);
-        // taps span [base - (bound-1), base + bound]; one texel of slack per side for the
-        // rare pixel whose own base is off by one (per-pixel path inside k_polar_pp)
-        t->org[ti] = bmin - (bound - 1) - 1;
-        t->extent = PL_MAX(t->extent, bmax - bmin + 2 * bound + 2);
-    }
-    return true;
-}
-
-static void free_axis_tiles(struct axis_tiles *t)
-{
-    free(t->loc);
-    free(t->list);
-    free(t->cnt);
-    free(t->org);
-    memset(t, 0, sizeof(*t));
-}
-
-static inline size_t align16(size_t x)
-{
-    return (x + 15) & ~(size_t) 15;
-}
-
-int plh_launch_polar_classify(plh_stream stream, const struct plh_pass *pass, void *out);
-int plh_launch_polar_weights(plh_stream stream, const struct plh_pass *pass, const float *clsx,
-                             int ncx, const float *clsy, int ncy, float *weights);
-
-
-/* ---- polar on the matrix pipe (device side: k_polar_mx.hiph, struct plh_polar_mx) ------- */
-
-// IEEE binary32 -> binary16, round to nearest even (subnormals and overflow included)
-static uint16_t f32_to_f16(float f)
-{
-    uint32_t x;
-    memcpy(&x, &f, 4);
-    const uint32_t sign = (x >> 16) & 0x8000u;
-    x &= 0x7fffffffu;
-    if (x >= 0x7f800000u)
-        return sign | (x > 0x7f800000u ? 0x7e00u : 0x7c00u);
-    if (x >= 0x477ff000u)   // rounds to >= 65520: infinity
-        return sign | 0x7c00u;
-    if (x < 0x38800000u) {  // below the smallest normal half: a multiple of 2^-24
-        const float scaled = fabsf(f) * 16777216.0f;       // exact
-        return sign | (uint16_t) lrintf(scaled);            // (round-half-even rounding mode)
-    }
-    const uint32_t mant = x & 0x007fffffu, exp = (x >> 23) - 112;
-    uint32_t h = (exp << 10) | (mant >> 13);
-    const uint32_t rest = mant & 0x1fffu;
-    if (rest > 0x1000u || (rest == 0x1000u && (h & 1)))
-        h++;                // (a carry into the exponent is the correct result)
-    return sign | (uint16_t) h;
-}
-
-static float f16_to_f32(uint16_t h)
-{
-    const int exp = (h >> 10) & 0x1f, mant = h & 0x3ff;
-    float v;
-    if (exp == 0)
-        v = ldexpf((float) mant, -24);
-    else if (exp == 31)
-        v = mant ? NAN : INFINITY;
-    else
-        v = ldexpf((float) (mant | 0x400), exp - 25);
-    return (h & 0x8000) ? -v : v;
-}
-
-// The geometry k_polar_mx covers: an axis whose outputs alternate between two phases and step
-// one source texel per two outputs (an exact 2x upscale, any sub-texel offset). Returns the
-// class of each parity and c1 = base(1) - base(0); false if the axis does not have that shape.
-static bool mx_axis(const float *fc, const int32_t *base, const uint16_t *ids, int len,
-                    int canon[2], int *c1)
-{
-    if (len < 2)
-        return false;
-    *c1 = base[1] - base[0];
-    if (*c1 != 0 && *c1 != 1)
-        return false;
-    for (int q = 0; q < 2; q++) {
-        canon[q] = ids[q];
-        // (a phase next to 0 or 1 could flip its base texel with the rounding of one pixel)
-        if (fc[q] < 0.02f || fc[q] > 0.98f)
-            return false;
-    }
-    for (int i = 0; i < len; i++) {
-        const int q = i & 1;
-        if (base[i] != base[0] + (i >> 1) + (q ? *c1 : 0))
-            return false;
-        // the phase of a column differs from its parity's by the fp32 rounding of the attribute
-        // interpolation, which grows with the coordinate: a few ulps of the source position
-        if (fabsf(fc[i] - fc[q]) > 1e-5f + 1.5f * FLT_EPSILON * (float) len)
-            return false;
-    }
-    return true;
-}
-
-static bool polar_mxd_build(pl_gpu gpu, pl_log log, struct sh_sampler_obj *obj,
-                            const struct plh_pass *pass, const float *wall, const uint32_t *taps,
-                            int ntaps, int ncx, int ncy, const float *clsx, const float *clsy,
-                            const float *colfc, const int32_t *colbase,
-                            const float *rowfc, const int32_t *rowbase);
-
-// B fragments (plh_device.h): frag f = 4 * (py * npairs + j) + kind, lane l, element e hold
-//   T(py, wy)[k][n] with n = l & 15, k = 8 * ((l >> 4) & 1) + e, wy = first[py] + 2 j + (l >> 5),
-//   = w'(phase py, phase n & 1, tap (k - dbx[n] - 3, wy - 3)): kind 0 / 1 its hi / lo f16 halves,
-//   kind 2 / 3 its derivative in fcoord_x / fcoord_y times 2^-PLH_MX_DSHIFT.
-// first[py] = the first tap row of row phase py that carries a weight for either column phase;
-// npairs = 3 when both row phases have at most six such rows (every centred 2x upscale with a
-// radius <= 3.25: rows -3 and 4 of the reference's 8 x 8 tap square lie 3.25 / 3.75 texels from
-// the sample), else 4.
-// The derivatives are the slopes of a least-squares line through the normalised weights of the
-// phase classes of that parity -- the weights the per-pixel kernels actually use for them.
-static bool polar_mx_build(pl_gpu gpu, pl_log log, struct sh_sampler_obj *obj,
-                           const struct plh_pass *pass, const float *wall, const uint32_t *taps,
-                           int ntaps, int ncx, int ncy, const float *clsx, const float *clsy,
-                           const float *colfc, const int32_t *colbase, const uint16_t *idx,
-                           const float *rowfc, const int32_t *rowbase, const uint16_t *idy)
-{
-    const struct plh_sampler_args *s = &pass->s;
-    const int W = pass->width, H = pass->height;
-    obj->mx_host = (struct plh_polar_mx) {0};
-    // LDS of the widest variant (RGBA tile, 4 wave-tile columns: 36 KiB of B fragments + 4 planes
-    // of 41 rows x 96 B; the RGB tile of 8 columns needs 55.5 KiB) against the limit the backend
-    // was created with (pl_hip_params.max_shmem_size)
-    if (gpu->glsl.max_shmem_size < 64 * 1024) {
-        pl_msg(log, PL_LOG_DEBUG, "matrix-pipe polar: needs 64 KiB of shared memory, the limit is %zu",
-               (size_t) gpu->glsl.max_shmem_size);
-        return false;
-    }
-    if (s->bound > 4 || s->tile_fp32 || s->address_mode != PLH_ADDRESS_CLAMP || pass->transpose ||
-        s->src.w < 2 || s->antiring > 0) {
-        pl_msg(log, PL_LOG_DEBUG, "matrix-pipe polar: not this pass (bound %d, fp32 tile %d, address "
-               "mode %d, transpose %d, antiring %g)", s->bound, s->tile_fp32, s->address_mode,
-               pass->transpose, s->antiring);
-        return false;
-    }
-    int cx[2], cy[2], c1x, c1y;
-    if (!mx_axis(colfc, colbase, idx, W, cx, &c1x) || !mx_axis(rowfc, rowbase, idy, H, cy, &c1y)) {
-        pl_msg(log, PL_LOG_DEBUG, "matrix-pipe polar: not an exact 2x geometry");
-        return false;
-    }
-
-    // tap (x, y) -> index in the list, x, y in [-3, 4]
-    int tap_at[8][8];
-    for (int y = 0; y < 8; y++) {
-        for (int x = 0; x < 8; x++)
-            tap_at[y][x] = -1;
-    }
-    for (int t = 0; t < ntaps; t++) {
-        const int x = (int8_t) (taps[t] & 0xff), y = (int8_t) ((taps[t] >> 8) & 0xff);
-        if (x < -3 || x > 4 || y < -3 || y > 4)
-            return false;
-        tap_at[y + 3][x + 3] = t;
-    }
-
-    // normalised weight (w * scale / wsum) of tap t for the class pair (kx, ky)
-#define WN(kx, ky, t) ((double) wall[((size_t) (ky) * ncx + (kx)) * (ntaps + 1) + (t)] * \
-                       (double) wall[((size_t) (ky) * ncx + (kx)) * (ntaps + 1) + ntaps])
-    // d w' / d fcoord along one axis at the class pair (cx[px], cy[py])
-    double *slope[2];       // [axis][(py * 2 + px) * ntaps + t]
-    slope[0] = calloc((size_t) 4 * PL_MAX(ntaps, 1), sizeof(double));
-    slope[1] = calloc((size_t) 4 * PL_MAX(ntaps, 1), sizeof(double));
-    const size_t nfx = ((size_t) W + PLH_MX_PAD - 1) / PLH_MX_PAD * PLH_MX_PAD;
-    const size_t nfy = ((size_t) H + PLH_MX_PAD - 1) / PLH_MX_PAD * PLH_MX_PAD;
-    const size_t frag_bytes = (size_t) PLH_MX_NFRAG * 64 * 8 * sizeof(uint16_t);
-    const size_t o_dfx = frag_bytes, o_dfy = o_dfx + nfx * 4;
-    const size_t o_sink = o_dfy + nfy * 4;      // (512 bytes nobody reads: plh_polar_mx.sink)
-    const size_t bytes = o_sink + 512;
-    uint8_t *blob = calloc(1, bytes);
-    if (!slope[0] || !slope[1] || !blob) {
-        free(slope[0]); free(slope[1]); free(blob);
-        return false;
-    }
-    for (int py = 0; py < 2; py++) {
-        for (int px = 0; px < 2; px++) {
-            double *sx = slope[0] + (size_t) (py * 2 + px) * ntaps;
-            double *sy = slope[1] + (size_t) (py * 2 + px) * ntaps;
-            double den = 0.0;
-            for (int c = 0; c < ncx; c++) {
-                const double d = (double) clsx[c] - (double) clsx[cx[px]];
-                if (fabs(d) > 0.01)
-                    continue;   // the other parity
-                den += d * d;
-                for (int t = 0; t < ntaps; t++)
-                    sx[t] += d * (WN(c, cy[py], t) - WN(cx[px], cy[py], t));
-            }
-            for (int t = 0; t < ntaps; t++)
-                sx[t] = den > 0.0 ? sx[t] / den : 0.0;
-            den = 0.0;
-            for (int c = 0; c < ncy; c++) {
-                const double d = (double) clsy[c] - (double) clsy[cy[py]];
-                if (fabs(d) > 0.01)
-                    continue;
-                den += d * d;
-                for (int t = 0; t < ntaps; t++)
-                    sy[t] += d * (WN(cx[px], c, t) - WN(cx[px], cy[py], t));
-            }
-            for (int t = 0; t < ntaps; t++)
-                sy[t] = den > 0.0 ? sy[t] / den : 0.0;
-        }
-    }
-
-    // live tap rows of each row phase: a row counts when any column phase has a weight, a slope
-    // included (the slopes are fitted through neighbouring classes, whose tap sets are the same:
-    // mx_axis holds every class of a parity within 1e-5 of it)
-    int first[2], npairs = 3;
-    for (int py = 0; py < 2; py++) {
-        int lo = 8, hi = -1;
-        for (int wy = 0; wy < 8; wy++) {
-            bool live = false;
-            for (int wx = 0; wx < 8 && !live; wx++) {
-                const int t = tap_at[wy][wx];
-                if (t < 0)
-                    continue;
-                for (int px = 0; px < 2 && !live; px++) {
-                    live = WN(cx[px], cy[py], t) != 0.0 ||
-                           slope[0][(size_t) (py * 2 + px) * ntaps + t] != 0.0 ||
-                           slope[1][(size_t) (py * 2 + px) * ntaps + t] != 0.0;
-                }
-            }
-            if (live) {
-                lo = PL_MIN(lo, wy);
-                hi = wy;
-            }
-        }
-        if (hi < lo)
-            lo = hi = 3;
-        first[py] = lo;
-        if (hi - lo + 1 > 6)
-            npairs = 4;
-    }
-    for (int py = 0; py < 2; py++)
-        first[py] = PL_MIN(first[py], 8 - 2 * npairs);  // (the pairs stay inside the 8 tap rows)
-
-    uint16_t *frag = (uint16_t *) blob;
-    const double dscale = ldexp(1.0, -PLH_MX_DSHIFT);
-    double worst = 0.0;
-    for (int py = 0; py < 2; py++) {
-        for (int j = 0; j < npairs; j++) {
-            for (int l = 0; l < 64; l++) {
-                const int n = l & 15, px = n & 1;
-                const int dbx = (n >> 1) + (px ? c1x : 0);
-                const int wy = first[py] + 2 * j + (l >> 5);
-                for (int e = 0; e < 8; e++) {
-                    const int k = 8 * ((l >> 4) & 1) + e, wx = k - dbx;
-                    double v = 0.0, vx = 0.0, vy = 0.0;
-                    if (wx >= 0 && wx < 8 && wy >= 0 && wy < 8 && tap_at[wy][wx] >= 0) {
-                        const int t = tap_at[wy][wx];
-                        v = WN(cx[px], cy[py], t);
-                        vx = slope[0][(size_t) (py * 2 + px) * ntaps + t];
-                        vy = slope[1][(size_t) (py * 2 + px) * ntaps + t];
-                    }
-                    const uint16_t hi = f32_to_f16((float) v);
-                    const uint16_t lo = f32_to_f16((float) (v - (double) f16_to_f32(hi)));
-                    const double err = fabs(v - (double) f16_to_f32(hi) - (double) f16_to_f32(lo));
-                    worst = PL_MAX(worst, err);
-                    const size_t f = 4 * (size_t) (py * npairs + j);
-                    frag[((f + 0) * 64 + l) * 8 + e] = hi;
-                    frag[((f + 1) * 64 + l) * 8 + e] = lo;
-                    frag[((f + 2) * 64 + l) * 8 + e] = f32_to_f16((float) (vx * dscale));
-                    frag[((f + 3) * 64 + l) * 8 + e] = f32_to_f16((float) (vy * dscale));
-                }
-            }
-        }
-    }
-#undef WN
-    free(slope[0]);
-    free(slope[1]);
-
-    // how far a pixel's own phase lies from the one its parity is expanded about
-    float *dfx = (float *) (blob + o_dfx), *dfy = (float *) (blob + o_dfy);
-    float dev = 0.0f;
-    const float up = ldexpf(1.0f, PLH_MX_DSHIFT);
-    for (int i = 0; i < W; i++) {
-        const float d = colfc[i] - colfc[i & 1];
-        dev = fmaxf(dev, fabsf(d));
-        dfx[i] = d * up;
-    }
-    for (int i = 0; i < H; i++) {
-        const float d = rowfc[i] - rowfc[i & 1];
-        dev = fmaxf(dev, fabsf(d));
-        dfy[i] = d * up;
-    }
-
-    pl_buf_destroy(gpu, &obj->mx_blob);
-    obj->mx_blob = pl_buf_create(gpu, pl_buf_params(.size = bytes, .storable = true,
-                                                    .initial_data = blob));
-    free(blob);
-    if (!obj->mx_blob)
-        return false;
-
-    const char *base = pl_hip_buf_ptr(obj->mx_blob);
-    obj->mx_host = (struct plh_polar_mx) {
-        .enabled = 1,
-        .org_x = colbase[0] - 3, .org_y = rowbase[0] - 3,
-        .npairs = npairs,
-        // tile row of tap row first[py] for the output row pair 0: rows 2 m + py sample from base
-        // rowbase[0] + m + (py ? c1y : 0)
-        .row_first = { first[0], first[1] + c1y },
-        .sink = (void *) (base + o_sink),
-        .bfrag = base,
-        .dfx = (const float *) (base + o_dfx), .dfy = (const float *) (base + o_dfy),
-    };
-    obj->mx_announced = false;
-    pl_msg(log, PL_LOG_DEBUG, "matrix-pipe tables for the polar pass: 2 x 2 phases (fcoord %.6f %.6f / %.6f %.6f, "
-           "per-pixel phases within %.2e: first-order terms), %d row pairs per phase from tile rows %d / %d, "
-           "weight split error <= %.2e",
-           colfc[0], colfc[1], rowfc[0], rowfc[1], dev, npairs, first[0], first[1] + c1y, worst);
-    return true;
-}
-
-// The geometry k_polar_mxr covers: an axis of an exact upscale by R : G (R outputs per G source
-// texels; G = 1: the integer ratios). Output i belongs to base index (i + shift) / R and phase
-// (i + shift) % R; the base texel of an output is origin + G * index + off[phase] with the same small
-// offset for every output of a phase (G = 1: none); the phase of an output is its phase class' up
-// to the fp32 rounding of the attribute interpolation. A phase at fcoord = 0 (odd integer ratios
-// have one) is where that rounding decides between (base b, fcoord +eps) and (base b - 1, fcoord
-// 1 - eps): the same sample position -- the tap that enters at one end and the one that leaves at
-// the other lie beyond the filter's radius -- so such an output is taken as (b, fcoord - 1), a small
-// negative deviation from the phase (`canon`: the outputs' canonical fcoord, which the caller turns
-// into the deviations). Returns the shift, the origin, the offsets and a representative, unwrapped
-// output of every phase.
-static bool mxr_axis(const float *fc, const int32_t *base, int len, int R, int G, int *shift,
-                     int *origin, int off[PLH_MXR_MAX_RATIO], int rep[PLH_MXR_MAX_RATIO], float *canon)
-{
-    if (len < 3 * R)
-        return false;
-    for (int i = 0; i < len; i++)
-        canon[i] = fc[i] > 0.98f ? fc[i] - 1.0f : fc[i];
-#define CANON_BASE(i) (base[i] + (fc[i] > 0.98f ? 1 : 0))
-    // the shift: the one under which the offsets are consistent and smallest
-    int best = -1, best_max = 0, best_org = 0;
-    for (int sh = 0; sh < R; sh++) {
-        int org = INT_MAX;
-        for (int i = 0; i < 2 * R; i++)
-            org = PL_MIN(org, CANON_BASE(i) - G * ((i + sh) / R));
-        int o[PLH_MXR_MAX_RATIO], omax = 0;
-        bool ok = true;
-        for (int q = 0; q < R; q++)
-            o[q] = -1;
-        for (int i = 0; i < len && ok; i++) {
-            const int q = (i + sh) % R;
-            const int d = CANON_BASE(i) - G * ((i + sh) / R) - org;
-            if (o[q] < 0)
-                o[q] = d;
-            ok = d == o[q] && d >= 0 && d <= (G == 1 ? 0 : 2);
-            omax = PL_MAX(omax, d);
-        }
-        if (ok && (best < 0 || omax < best_max)) {
-            best = sh;
-            best_max = omax;
-            best_org = org;
-        }
-    }
-    if (best < 0)
-        return false;
-    *shift = best;
-    *origin = best_org;
-    for (int q = 0; q < R; q++)
-        rep[q] = off[q] = -1;
-    for (int i = 0; i < len; i++) {
-        const int q = (i + best) % R;
-        if (off[q] < 0)
-            off[q] = CANON_BASE(i) - G * ((i + best) / R) - best_org;
-        if (rep[q] < 0 && !(fc[i] > 0.98f))
-            rep[q] = i;
-    }
-#undef CANON_BASE
-    for (int q = 0; q < R; q++) {
-        if (rep[q] < 0 || off[q] < 0)
-            return false;
-    }
-    for (int i = 0; i < len; i++) {
-        const int q = (i + best) % R;
-        if (fabsf(canon[i] - fc[rep[q]]) > 1e-5f + 1.5f * FLT_EPSILON * (float) len)
-            return false;
-    }
-    return true;
-}
-
-// Test hook (tests/test_mxr_axis.py, CPU): mxr_axis on an axis described by its per-output base
-// texels and fcoords. out = { shift, origin, off[0..3], rep[0..3] }; canon: len floats.
-PL_API int plh_test_mxr_axis(const float *fc, const int32_t *base, int len, int R, int G,
-                             int *out, float *canon);
-int plh_test_mxr_axis(const float *fc, const int32_t *base, int len, int R, int G, int *out, float *canon)
-{
-    int shift = 0, origin = 0, off[PLH_MXR_MAX_RATIO] = {0}, rep[PLH_MXR_MAX_RATIO] = {0};
-    if (R < 2 || R > PLH_MXR_MAX_RATIO || !mxr_axis(fc, base, len, R, G, &shift, &origin, off, rep, canon))
-        return 0;
-    out[0] = shift;
-    out[1] = origin;
-    for (int q = 0; q < PLH_MXR_MAX_RATIO; q++) {
-        out[2 + q] = q < R ? off[q] : -1;
-        out[2 + PLH_MXR_MAX_RATIO + q] = q < R ? rep[q] : -1;
-    }
-    return 1;
-}
-
-// B fragments of k_polar_mxr (plh_device.h): frag f = 32 py + 4 * (NH * j + h) + kind, lane l,
-// element e hold T(py, j, h)[k][n], n = l & 15 the output column within half h of the wave's 8 / G
-// bases -- base bi = 4 h + n / R, phase px = n % R, n < 4 R -- and K index (row 2 j + (l >> 5) of the
-// base's footprint rows, column k = 8 * ((l >> 4) & 1) + e of the wave's 16-column window):
-//   = w'(py, px, tap (k - G bi - offx[px] - 3, 2 j + (l >> 5) - offy[py] - 3)), kinds as in
-// polar_mx_build. NH halves and NJ row pairs: 2 and 4 for the integer ratios, 1 and 5 for 3 : 2.
-static bool polar_mxr_build(pl_gpu gpu, pl_log log, struct sh_sampler_obj *obj,
-                            const struct plh_pass *pass, const float *wall, const uint32_t *taps,
-                            int ntaps, int ncx, int ncy, const float *clsx, const float *clsy,
-                            const float *colfc, const int32_t *colbase, const uint16_t *idx,
-                            const float *rowfc, const int32_t *rowbase, const uint16_t *idy)
-{
-    const struct plh_sampler_args *s = &pass->s;
-    const int W = pass->width, H = pass->height;
-    if (gpu->glsl.max_shmem_size < 64 * 1024 || s->bound > 4 || s->tile_fp32 ||
-        s->address_mode != PLH_ADDRESS_CLAMP || pass->transpose || s->src.w < 2 || s->antiring > 0)
-        return false;
-    int R = 0, G = 0, sx = 0, sy = 0, repx[PLH_MXR_MAX_RATIO], repy[PLH_MXR_MAX_RATIO];
-    int bx0 = 0, by0 = 0, offx[PLH_MXR_MAX_RATIO], offy[PLH_MXR_MAX_RATIO];
-    float *canx = malloc(((size_t) W + H) * sizeof(float)), *cany = canx ? canx + W : NULL;
-    if (!canx)
-        return false;
-    static const int ratios[][2] = { {3, 1}, {4, 1}, {3, 2} };
-    for (int r = 0; r < 3 && !R; r++) {
-        if (mxr_axis(colfc, colbase, W, ratios[r][0], ratios[r][1], &sx, &bx0, offx, repx, canx) &&
-            mxr_axis(rowfc, rowbase, H, ratios[r][0], ratios[r][1], &sy, &by0, offy, repy, cany)) {
-            R = ratios[r][0];
-            G = ratios[r][1];
-        }
-    }
-    if (!R) {
-        pl_msg(log, PL_LOG_DEBUG, "matrix-pipe polar: not an exact 3x / 4x / 3 : 2 geometry either");
-        free(canx);
-        return false;
-    }
-    const int NJ = G == 1 ? 4 : 5, NH = G == 1 ? 2 : 1;
-    int tap_at[8][8];
-    for (int y = 0; y < 8; y++) {
-        for (int x = 0; x < 8; x++)
-            tap_at[y][x] = -1;
-    }
-    for (int t = 0; t < ntaps; t++) {
-        const int x = (int8_t) (taps[t] & 0xff), y = (int8_t) ((taps[t] >> 8) & 0xff);
-        if (x < -3 || x > 4 || y < -3 || y > 4) {
-            free(canx);
-            return false;
-        }
-        tap_at[y + 3][x + 3] = t;
-    }
-#define WN(kx, ky, t) ((double) wall[((size_t) (ky) * ncx + (kx)) * (ntaps + 1) + (t)] * \
-                       (double) wall[((size_t) (ky) * ncx + (kx)) * (ntaps + 1) + ntaps])
-    int cx[PLH_MXR_MAX_RATIO], cy[PLH_MXR_MAX_RATIO];
-    for (int q = 0; q < R; q++) {
-        cx[q] = idx[repx[q]];
-        cy[q] = idy[repy[q]];
-    }
-    // d w' / d fcoord at every phase pair: least-squares slopes over the classes of that phase
-    const size_t nt = (size_t) PL_MAX(ntaps, 1);
-    double *slx = calloc((size_t) R * R * nt, sizeof(double)), *sly = calloc((size_t) R * R * nt, sizeof(double));
-    const size_t nfx = ((size_t) W + PLH_MX_PAD - 1) / PLH_MX_PAD * PLH_MX_PAD;
-    const size_t nfy = ((size_t) H + PLH_MX_PAD - 1) / PLH_MX_PAD * PLH_MX_PAD;
-    const size_t frag_bytes = (size_t) R * PLH_MXR_FRAGS_PER_PHASE * 64 * 8 * sizeof(uint16_t);
-    const size_t o_dfx = frag_bytes, o_dfy = o_dfx + nfx * 4, bytes = o_dfy + nfy * 4;
-    uint8_t *blob = calloc(1, bytes);
-    if (!slx || !sly || !blob) {
-        free(slx); free(sly); free(blob); free(canx);
-        return false;
-    }
-    // tap t sits at (tapx[t], tapy[t]) of the 8 x 8 footprint
-    int tapx[64], tapy[64];
-    for (int y = 0; y < 8; y++) {
-        for (int x = 0; x < 8; x++) {
-            if (tap_at[y][x] >= 0 && tap_at[y][x] < 64) {
-                tapx[tap_at[y][x]] = x;
-                tapy[tap_at[y][x]] = y;
-            }
-        }
-    }
-    if (ntaps > 64) {
-        free(slx); free(sly); free(blob); free(canx);
-        return false;
-    }
-    // The classes a slope is fitted through: those within 0.01 of the phase -- and, for the phase at
-    // fcoord = 0 of an odd ratio, the WRAPPED ones on the other side of it (fcoord 1 - eps on the
-    // base one texel lower = -eps on this base: their weight for footprint position (x, y) is their
-    // own weight one position further along the axis). Without them that phase may have a single
-    // class, fcoord = 0 exactly, no slope, and its wrapped outputs -- up to 1e-4 away -- no
-    // first-order term (4 codes on white noise at 720p -> 4K).
-    for (int py = 0; py < R; py++) {
-        for (int px = 0; px < R; px++) {
-            double *vx = slx + (size_t) (py * R + px) * nt, *vy = sly + (size_t) (py * R + px) * nt;
-            double den = 0.0;
-            for (int c = 0; c < ncx; c++) {
-                const bool wrapped = clsx[c] > 0.98f;
-                const double d = (double) clsx[c] - (wrapped ? 1.0 : 0.0) - (double) clsx[cx[px]];
-                if (fabs(d) > 0.01)
-                    continue;   // another phase
-                den += d * d;
-                for (int t = 0; t < ntaps; t++) {
-                    const int ts = !wrapped ? t : tapx[t] + 1 < 8 ? tap_at[tapy[t]][tapx[t] + 1] : -1;
-                    vx[t] += d * ((ts >= 0 ? WN(c, cy[py], ts) : 0.0) - WN(cx[px], cy[py], t));
-                }
-            }
-            for (int t = 0; t < ntaps; t++)
-                vx[t] = den > 0.0 ? vx[t] / den : 0.0;
-            den = 0.0;
-            for (int c = 0; c < ncy; c++) {
-                const bool wrapped = clsy[c] > 0.98f;
-                const double d = (double) clsy[c] - (wrapped ? 1.0 : 0.0) - (double) clsy[cy[py]];
-                if (fabs(d) > 0.01)
-                    continue;
-                den += d * d;
-                for (int t = 0; t < ntaps; t++) {
-                    const int ts = !wrapped ? t : tapy[t] + 1 < 8 ? tap_at[tapy[t] + 1][tapx[t]] : -1;
-                    vy[t] += d * ((ts >= 0 ? WN(cx[px], c, ts) : 0.0) - WN(cx[px], cy[py], t));
-                }
-            }
-            for (int t = 0; t < ntaps; t++)
-                vy[t] = den > 0.0 ? vy[t] / den : 0.0;
-        }
-    }
-    uint16_t *frag = (uint16_t *) blob;
-    const double dscale = ldexp(1.0, -PLH_MX_DSHIFT);
-    double worst = 0.0;
-    for (int py = 0; py < R; py++) {
-        for (int j = 0; j < NJ; j++) {
-            for (int h = 0; h < NH; h++) {
-                const size_t f = (size_t) py * PLH_MXR_FRAGS_PER_PHASE + 4 * (size_t) (NH * j + h);
-                for (int l = 0; l < 64; l++) {
-                    const int n = l & 15, px = n % R, bi = 4 * h + n / R;
-                    const int wy = 2 * j + (l >> 5) - offy[py];
-                    for (int e = 0; e < 8; e++) {
-                        const int k = 8 * ((l >> 4) & 1) + e, wx = k - G * bi - offx[px];
-                        double v = 0.0, vx = 0.0, vy = 0.0;
-                        if (n < 4 * R && wx >= 0 && wx < 8 && wy >= 0 && wy < 8 && tap_at[wy][wx] >= 0) {
-                            const int t = tap_at[wy][wx];
-                            v = WN(cx[px], cy[py], t);
-                            vx = slx[(size_t) (py * R + px) * nt + t];
-                            vy = sly[(size_t) (py * R + px) * nt + t];
-                        }
-                        const uint16_t hi = f32_to_f16((float) v);
-                        const uint16_t lo = f32_to_f16((float) (v - (double) f16_to_f32(hi)));
-                        worst = PL_MAX(worst, fabs(v - (double) f16_to_f32(hi) - (double) f16_to_f32(lo)));
-                        frag[((f + 0) * 64 + l) * 8 + e] = hi;
-                        frag[((f + 1) * 64 + l) * 8 + e] = lo;
-                        frag[((f + 2) * 64 + l) * 8 + e] = f32_to_f16((float) (vx * dscale));
-                        frag[((f + 3) * 64 + l) * 8 + e] = f32_to_f16((float) (vy * dscale));
-                    }
-                }
-            }
-        }
-    }
-#undef WN
-    free(slx);
-    free(sly);
-    float *dfx = (float *) (blob + o_dfx), *dfy = (float *) (blob + o_dfy);
-    float dev = 0.0f;
-    const float up = ldexpf(1.0f, PLH_MX_DSHIFT);
-    for (int i = 0; i < W; i++) {
-        const float d = canx[i] - colfc[repx[(i + sx) % R]];
-        dev = fmaxf(dev, fabsf(d));
-        dfx[i] = d * up;
-    }
-    for (int i = 0; i < H; i++) {
-        const float d = cany[i] - rowfc[repy[(i + sy) % R]];
-        dev = fmaxf(dev, fabsf(d));
-        dfy[i] = d * up;
-    }
-    free(canx);
-    pl_buf_destroy(gpu, &obj->mx_blob);
-    obj->mx_blob = pl_buf_create(gpu, pl_buf_params(.size = bytes, .storable = true, .initial_data = blob));
-    free(blob);
-    if (!obj->mx_blob)
-        return false;
-    const char *base = pl_hip_buf_ptr(obj->mx_blob);
-    obj->mx_host = (struct plh_polar_mx) {
-        .enabled = 3, .ratio = R, .group = G, .sx = sx, .sy = sy,
-        .org_x = bx0 - 3, .org_y = by0 - 3,     // (bx0, by0: the texel of base index 0, offset 0)
-        .bfrag = base,
-        .dfx = (const float *) (base + o_dfx), .dfy = (const float *) (base + o_dfy),
-    };
-    obj->mx_announced = false;
-    pl_msg(log, PL_LOG_DEBUG, "matrix-pipe tables for the polar pass: %d x %d phases (%d : %d upscale, shifts %d / %d, "
-           "per-pixel phases within %.2e: first-order terms), weight split error <= %.2e", R, R, R, G, sx, sy, dev, worst);
-    return true;
-}
-
-static bool polar_pp_build(pl_gpu gpu, pl_log log, struct sh_sampler_obj *obj,
-                           const struct plh_pass *pass)
-{
-    const struct plh_sampler_args *s = &pass->s;
-    const int W = pass->width, H = pass->height, ntaps = s->num_taps;
-    const plh_stream stream = plh_gpu_stream(gpu);
-    bool ok = false;
-    pl_buf tmp = NULL, wbuf = NULL;
-    float *host = NULL, *clsx = NULL, *clsy = NULL, *wall = NULL;
-    uint16_t *idx = NULL, *idy = NULL;
-    uint8_t *blob = NULL;
-    struct axis_tiles tx = {0}, ty = {0};
-    enum { MAX_CLS = 96 };
-
-    // ---- 1. fcoord / base of every column and row, evaluated by the device ------------------
-    const size_t cls_bytes = (size_t) 2 * (W + H) * 4;
-    tmp = pl_buf_create(gpu, pl_buf_params(.size = cls_bytes, .storable = true,
-                                           .host_readable = true));
-    host = malloc(cls_bytes);
-    clsx = malloc(MAX_CLS * sizeof(float));
-    clsy = malloc(MAX_CLS * sizeof(float));
-    idx = malloc(W * sizeof(uint16_t));
-    idy = malloc(H * sizeof(uint16_t));
-    if (!tmp || !host || !clsx || !clsy || !idx || !idy)
-        goto done;
-    if (plh_launch_polar_classify(stream, pass, pl_hip_buf_ptr(tmp)) ||
-        !plh_buf_read(gpu, tmp, 0, host, cls_bytes))
-        goto done;
-    const float *colfc = host, *rowfc = host + 2 * W;
-    const int32_t *colbase = (const int32_t *) (host + W);
-    const int32_t *rowbase = (const int32_t *) (host + 2 * W + H);
-
-    // ---- 2. classes ---------------------------------------------------------------------------
-    const int ncx = classify_axis(colfc, W, clsx, idx, MAX_CLS);
-    const int ncy = classify_axis(rowfc, H, clsy, idy, MAX_CLS);
-    if (ncx < 0 || ncy < 0) {
-        // arbitrary (non-rational) ratio: every column has its own phase
-        pl_msg(log, PL_LOG_DEBUG, "polar phase classes: more than %d distinct phases per axis "
-               "(%dx%d outputs)", MAX_CLS, W, H);
-        goto done;
-    }
-
-    // ---- 3. outputs per lane: 2x2 when pairs of outputs share their base texel --------------
-    int n = 1, padx = 0, pady = 0;
-    for (int px = 0; px < 2 && n == 1; px++) {
-        if (!cells_share_base(colbase, W, 2, px))
-            continue;
-        for (int py = 0; py < 2; py++) {
-            if (cells_share_base(rowbase, H, 2, py)) {
-                n = 2; padx = px; pady = py;
-                break;
-            }
-        }
-    }
-
-    // ---- 4. tiles: 32 x 8*rows cells, LDS = lut + weights + source tile ----------------------
-    const size_t texel = s->tile_fp32 ? 16 : 8;
-    const size_t max_lds = 64 * 1024;   // >= 2 workgroups per CU
-    int rows = n == 2 ? 3 : 4, tp = 0, ntc = 0;    // (measured: 3 beats 4 by ~2 % for 2x2 cells)
-    const int rows_forced = plh_switch(PLH_SW_PP_ROWS);     // profiling aid
-    if (rows_forced > 0)
-        rows = PL_MIN(rows_forced, 8);
-    rows = PL_MIN(rows, 64 / (POLAR_BH * n));   // the kernel stages <= 64 output rows of info
-    // a small output (the chroma planes of 1080p video: 1920 x 1080 = 690 workgroups at 3 rows) does
-    // not fill 256 CUs twice with such tiles, and the kernel lives on latency hiding: fewer rows
-    // per workgroup until there are two rounds of them (NV12 1080p -> 4K, the chroma pass:
-    // 37.5 -> 26.2 us, profiles/r04_49_pp_rows_small.txt)
-    if (rows_forced <= 0) {
-        while (rows > 1 && (size_t) ((W + POLAR_BW * n - 1) / (POLAR_BW * n)) *
-                           (size_t) ((H + POLAR_BH * rows * n - 1) / (POLAR_BH * rows * n)) < 1024)
-            rows--;
-    }
-    size_t lds_w = 0;
-    for (;; rows >>= 1) {
-        free_axis_tiles(&tx);
-        free_axis_tiles(&ty);
-        if (!build_axis_tiles(&tx, idx, colbase, W, n, padx, POLAR_BW, s->bound) ||
-            !build_axis_tiles(&ty, idy, rowbase, H, n, pady, POLAR_BH * rows, s->bound))
-            goto done;
-        // worst-case weights slice; the compacted tap count is only known later
-        lds_w = align16((size_t) tx.max_cnt * ty.max_cnt * (ntaps + 4) * 4) + align16(ntaps * 4);
-        if (2048 + 1024 + 64 + lds_w + (size_t) tx.extent * ty.extent * texel <= max_lds)
-            break;
-        if (rows == 1)
-            goto done;
-    }
-
-    // ---- 5. weights of every class pair, by the device; compaction of dead taps -------------
-    const size_t wall_bytes = (size_t) ncx * ncy * (ntaps + 1) * 4;
-    wbuf = pl_buf_create(gpu, pl_buf_params(.size = wall_bytes + (ncx + ncy) * 4, .storable = true,
-                                            .host_readable = true, .host_writable = true));
-    wall = malloc(wall_bytes);
-    if (!wbuf || !wall)
-        goto done;
-    plh_buf_write(gpu, wbuf, wall_bytes, clsx, ncx * 4);
-    plh_buf_write(gpu, wbuf, wall_bytes + ncx * 4, clsy, ncy * 4);
-    const float *dcls = (const float *) ((const char *) pl_hip_buf_ptr(wbuf) + wall_bytes);
-    if (plh_launch_polar_weights(stream, pass, dcls, ncx, dcls + ncx, ncy, pl_hip_buf_ptr(wbuf)) ||
-        !plh_buf_read(gpu, wbuf, 0, wall, wall_bytes))
-        goto done;
-
-    uint32_t *taps_all = malloc(PL_MAX(ntaps, 1) * sizeof(uint32_t));
-    int *keep = malloc(PL_MAX(ntaps, 1) * sizeof(int));
-    if (!taps_all || !keep || !plh_buf_read(gpu, obj->taps, 0, taps_all, ntaps * sizeof(uint32_t))) {
-        free(taps_all);
-        free(keep);
-        goto done;
-    }
-    for (int t = 0; t < ntaps; t++) {
-        bool used = false;
-        for (int pr = 0; pr < ncx * ncy && !used; pr++)
-            used = wall[(size_t) pr * (ntaps + 1) + t] != 0.0f;
-        if (used)
-            keep[ntc++] = t;
-    }
-    tp = (ntc + 1 + 3) & ~3;    // weights + norm, padded to 16 bytes
-    // + the compacted tap offsets, staged at the tail of this area (k_polar_pp)
-    lds_w = align16((size_t) tx.max_cnt * ty.max_cnt * tp * 4) + align16(ntc * 4);
-
-    // ---- 6. one device blob: struct + tables ---------------------------------------------------
-    size_t off = align16(sizeof(struct plh_polar_pp));
-#define PLACE(name, bytes) const size_t o_##name = off; off = align16(off + (bytes))
-    PLACE(colfc, (size_t) W * 4);   PLACE(rowfc, (size_t) H * 4);
-    PLACE(colbase, (size_t) W * 4); PLACE(rowbase, (size_t) H * 4);
-    PLACE(colloc, W);               PLACE(rowloc, H);
-    PLACE(collist, (size_t) tx.ntiles * PLH_PP_LMAX * 2);
-    PLACE(rowlist, (size_t) ty.ntiles * PLH_PP_LMAX * 2);
-    PLACE(coln, (size_t) tx.ntiles * 4); PLACE(rown, (size_t) ty.ntiles * 4);
-    PLACE(colorg, (size_t) tx.ntiles * 4); PLACE(roworg, (size_t) ty.ntiles * 4);
-    PLACE(weights, (size_t) ncx * ncy * tp * 4);
-    PLACE(tapoff, (size_t) PL_MAX(ntc, 1) * 4);
-    PLACE(tilemap, (size_t) tx.ntiles * ty.ntiles * 4);
-#undef PLACE
-    blob = calloc(1, off);
-    if (!blob) {
-        free(taps_all);
-        free(keep);
-        goto done;
-    }
-    memcpy(blob + o_colfc, colfc, (size_t) W * 4);
-    memcpy(blob + o_rowfc, rowfc, (size_t) H * 4);
-    memcpy(blob + o_colbase, colbase, (size_t) W * 4);
-    memcpy(blob + o_rowbase, rowbase, (size_t) H * 4);
-    memcpy(blob + o_colloc, tx.loc, W);
-    memcpy(blob + o_rowloc, ty.loc, H);
-    memcpy(blob + o_collist, tx.list, (size_t) tx.ntiles * PLH_PP_LMAX * 2);
-    memcpy(blob + o_rowlist, ty.list, (size_t) ty.ntiles * PLH_PP_LMAX * 2);
-    for (int i = 0; i < tx.ntiles; i++)
-        ((int32_t *) (blob + o_coln))[i] = tx.cnt[i];
-    for (int i = 0; i < ty.ntiles; i++)
-        ((int32_t *) (blob + o_rown))[i] = ty.cnt[i];
-    memcpy(blob + o_colorg, tx.org, (size_t) tx.ntiles * 4);
-    memcpy(blob + o_roworg, ty.org, (size_t) ty.ntiles * 4);
-    float *wc = (float *) (blob + o_weights);
-    for (int pr = 0; pr < ncx * ncy; pr++) {
-        const float *src = wall + (size_t) pr * (ntaps + 1);
-        float *dst = wc + (size_t) pr * tp;
-        for (int k = 0; k < ntc; k++)
-            dst[k] = src[keep[k]];
-        dst[ntc] = src[ntaps];      // scale / wsum
-    }
-    int32_t *tapoff = (int32_t *) (blob + o_tapoff);
-    for (int k = 0; k < ntc; k++) {
-        const uint32_t tap = taps_all[keep[k]];
-        const int x = (int8_t) (tap & 0xff), y = (int8_t) ((tap >> 8) & 0xff);
-        tapoff[k] = (y * tx.extent + x) * (int) texel;
-    }
-    // the same geometry on the matrix pipe, where it has the shape for it
-    if (!polar_mx_build(gpu, log, obj, pass, wall, taps_all, ntaps, ncx, ncy, clsx, clsy, colfc, colbase,
-                        idx, rowfc, rowbase, idy) &&
-        !polar_mxr_build(gpu, log, obj, pass, wall, taps_all, ntaps, ncx, ncy, clsx, clsy, colfc, colbase,
-                         idx, rowfc, rowbase, idy))
-        polar_mxd_build(gpu, log, obj, pass, wall, taps_all, ntaps, ncx, ncy, clsx, clsy, colfc, colbase,
-                        rowfc, rowbase);
-    free(taps_all);
-    free(keep);
-
-    // XCD-aware launch order: workgroups go to the 8 XCDs round-robin, each XCD has its own L2;
-    // XCD x gets the x-th contiguous eighth of the tiles so that neighbours share halo texels
-    const uint32_t gx = tx.ntiles, total = (uint32_t) tx.ntiles * ty.ntiles;
-    const bool remap = n == 2 && tx.ntiles <= 0xffff && ty.ntiles <= 0xffff;
-    if (remap) {
-        uint32_t *tm = (uint32_t *) (blob + o_tilemap);
-        const uint32_t q = total / 8, r = total % 8;
-        for (uint32_t lin = 0; lin < total; lin++) {
-            const uint32_t xcd = lin % 8, k = lin / 8;
-            const uint32_t tile = xcd * q + PL_MIN(xcd, r) + k;
-            tm[lin] = (tile % gx) | ((tile / gx) << 16);
-        }
-    }
-
-    pl_buf_destroy(gpu, &obj->pp_blob);
-    obj->pp_blob = pl_buf_create(gpu, pl_buf_params(.size = off, .storable = true,
-                                                    .host_writable = true));
-    if (!obj->pp_blob)
-        goto done;
-    const char *d = pl_hip_buf_ptr(obj->pp_blob);
-    struct plh_polar_pp *pp = &obj->pp_host;
-    *pp = (struct plh_polar_pp) {
-        .n = n, .padx = padx, .pady = pady,
-        .cells_w = (W + padx + n - 1) / n, .cells_h = (H + pady + n - 1) / n,
-        .ncx = ncx, .ncy = ncy, .ntaps = ntc, .tp = tp,
-        .colfc = (const float *) (d + o_colfc), .rowfc = (const float *) (d + o_rowfc),
-        .colbase = (const int32_t *) (d + o_colbase), .rowbase = (const int32_t *) (d + o_rowbase),
-        .colloc = (const uint8_t *) (d + o_colloc), .rowloc = (const uint8_t *) (d + o_rowloc),
-        .collist = (const uint16_t *) (d + o_collist), .rowlist = (const uint16_t *) (d + o_rowlist),
-        .coln = (const int32_t *) (d + o_coln), .rown = (const int32_t *) (d + o_rown),
-        .colorg = (const int32_t *) (d + o_colorg), .roworg = (const int32_t *) (d + o_roworg),
-        .weights = (const float *) (d + o_weights), .tapoff = (const int32_t *) (d + o_tapoff),
-        .tilemap = remap ? (const uint32_t *) (d + o_tilemap) : NULL,
-    };
-    memcpy(blob, pp, sizeof(*pp));
-    plh_buf_write(gpu, obj->pp_blob, 0, blob, off);
-
-    obj->pp_tile_w = tx.extent;
-    obj->pp_tile_h = ty.extent;
-    obj->pp_rows = rows;
-    obj->pp_lds_weights = lds_w;
-    pl_msg(log, PL_LOG_DEBUG, "polar phase classes: %dx%d classes, %d/%d live taps, %dx%d px per "
-           "lane, tile %dx%d, %d rows, %zu B of weights in LDS", ncx, ncy, ntc, ntaps, n, n,
-           tx.extent, ty.extent, rows, lds_w);
-    ok = true;
-
-done:
-    pl_buf_destroy(gpu, &tmp);
-    pl_buf_destroy(gpu, &wbuf);
-    free_axis_tiles(&tx);
-    free_axis_tiles(&ty);
-    free(host); free(clsx); free(clsy); free(idx); free(idy); free(wall); free(blob);
-    return ok;
-}
-
-void plh_polar_pp_setup(pl_gpu gpu, pl_log log, void *polar_obj, struct plh_pass *pass)
-{
-    struct sh_sampler_obj *obj = polar_obj;
-    struct plh_sampler_args *s = &pass->s;
-    s->pp = NULL;
-    memset(&s->mx, 0, sizeof(s->mx));
-    if (plh_switch(PLH_SW_POLAR_PER_PIXEL))
-        return;
-    const uint32_t cm = s->comp_mask & 0xf;
-    if (cm != 0x7 && cm != 0xf && cm != 0x1 && cm != 0x3)
-        return; // k_polar_pp is instantiated for RGB / RGBA and for 1- / 2-component planes
-
-    struct polar_pp_key key = {
-        .src_w = s->src.w, .src_h = s->src.h, .width = pass->width, .height = pass->height,
-        .bound = s->bound, .num_taps = s->num_taps, .fp32_tile = s->tile_fp32,
-        .scale = s->scale, .radius = s->radius, .filter_gen = obj->filter_gen,
-    };
-    memcpy(key.pos, s->pos, sizeof(key.pos));
-    if (!obj->pp_state || memcmp(&key, &obj->pp_key, sizeof(key))) {
-        obj->pp_key = key;
-        obj->pp_state = polar_pp_build(gpu, log, obj, pass) ? 1 : -1;
-        if (obj->pp_state < 0)
-            pl_msg(log, PL_LOG_DEBUG, "polar phase classes not applicable to this geometry; "
-                   "using per-pixel weights");
-    }
-    if (obj->pp_state != 1)
-        return;
-
-    s->pp = pl_hip_buf_ptr(obj->pp_blob);
-    s->ppv = obj->pp_host;
-    s->pp_n = obj->pp_host.n;
-    s->pp_cells_w = obj->pp_host.cells_w;
-    s->pp_cells_h = obj->pp_host.cells_h;
-    s->pp_lds_weights = obj->pp_lds_weights;
-    s->pp_debug = plh_switch(PLH_SW_PP_DEBUG);
-    s->tile_w = obj->pp_tile_w;
-    s->tile_h = obj->pp_tile_h;
-    s->tile_rows = obj->pp_rows;
-
-    // k_polar_mx: the contraction on the f16 matrix pipe, within +-1 code of 16 bits of the
-    // sequential-fma kernels. PL_HIP_POLAR_MFMA=0 keeps the bit-exact reference variant.
-    // That bound holds behind EVERY epilogue, the ones that amplify near black included -- a pass
-    // that scales in linear / sigmoidized light continues with UNSIGMOIDIZE (slope up to 17 at
-    // the dark end) and DELINEARIZE ((1 / 2.4) x^-0.58) -- because the contraction's error scales
-    // with the taps' products, which are small where the output is dark: measured <= 1 code at
-    // 1080p -> 4K on white noise and on a dark field with isolated full-scale texels
-    // (tests/test_gpu_default_kernels.py::test_matrix_pipe_behind_sigmoid_measured).
-    memset(&s->mx, 0, sizeof(s->mx));
-    if (obj->mx_host.enabled && plh_switch(PLH_SW_POLAR_MFMA) && (cm == 0x7 || cm == 0xf) &&
-        !pass->transpose && s->address_mode == PLH_ADDRESS_CLAMP) {
-        s->mx = obj->mx_host;
-        if (!obj->mx_announced)
-            pl_msg(log, PL_LOG_DEBUG, "polar on the matrix pipe (%s)",
-                   s->mx.enabled == 2 ? "k_polar_mxd, where the pass has its shape" :
-                   s->mx.enabled == 3 ? "k_polar_mxr, where the pass has its shape" : "k_polar_mx");
-        obj->mx_announced = true;
-    }
-}
-
-
-/* ---- the 2 : 1 downscale on the matrix pipe ------------------------------------------------------ */
-
-// every output i has its base texel at base[0] + 2 i and a phase within `tol` of 1/2
-static bool mxd_axis(const float *fc, const int32_t *base, int len, float *dev)
-{
-    if (len < 2)
-        return false;
-    for (int i = 0; i < len; i++) {
-        if (base[i] != base[0] + 2 * i)
-            return false;
-        const float d = fabsf(fc[i] - 0.5f);
-        // (first-order expansion about 1/2: its neglected term is (d / a texel)^2 of a weight)
-        if (d > 4e-3f)
-            return false;
-        *dev = fmaxf(*dev, d);
-    }
-    return true;
-}
-
-// B fragments of k_polar_mxd (plh_device.h): frag f = 4 * (2 j + kb) + kind, lane l, element e hold
-//   T_j[i], i = 32 kb + k - 2 n, n = l & 15, k = 8 * (l >> 4) + e  (0 outside the 14 taps),
-// T_j[i] = the normalised weight w' of tap (i - 6, j - 6) at fcoord (1/2, 1/2) -- kind 0 / 1 its f16
-// hi / lo halves -- and kind 2 / 3 its derivative in fcoord_x / fcoord_y (least-squares slope over
-// the phase classes that occur) times 2^-PLH_MX_DSHIFT. Rows j and 13 - j are averaged (they agree
-// to rounding: the distance of a tap to the sample point is the same).
-static bool polar_mxd_build(pl_gpu gpu, pl_log log, struct sh_sampler_obj *obj,
-                            const struct plh_pass *pass, const float *wall, const uint32_t *taps,
-                            int ntaps, int ncx, int ncy, const float *clsx, const float *clsy,
-                            const float *colfc, const int32_t *colbase,
-                            const float *rowfc, const int32_t *rowbase)
-{
-    const struct plh_sampler_args *s = &pass->s;
-    const int W = pass->width, H = pass->height;
-    enum { NT = PLH_MXD_TAPS };
-    if (s->tile_fp32 || s->address_mode != PLH_ADDRESS_CLAMP || pass->transpose || s->src.w < 2 ||
-        s->antiring > 0)
-        return false;
-    // (56 KiB of B fragments + a 140 x 76 tile of three f16 planes: one workgroup per CU)
-    if (gpu->glsl.max_shmem_size < 124 * 1024) {
-        pl_msg(log, PL_LOG_DEBUG, "matrix-pipe downscale: needs 124 KiB of shared memory, the limit is %zu",
-               (size_t) gpu->glsl.max_shmem_size);
-        return false;
-    }
-    float dev = 0.0f;
-    if (!mxd_axis(colfc, colbase, W, &dev) || !mxd_axis(rowfc, rowbase, H, &dev))
-        return false;
-    // the class pair at exactly (1/2, 1/2): the expansion point
-    int c0x = -1, c0y = -1;
-    for (int c = 0; c < ncx; c++)
-        c0x = clsx[c] == 0.5f ? c : c0x;
-    for (int c = 0; c < ncy; c++)
-        c0y = clsy[c] == 0.5f ? c : c0y;
-    if (c0x < 0 || c0y < 0) {
-        pl_msg(log, PL_LOG_DEBUG, "matrix-pipe downscale: no output at phase 1/2 exactly");
-        return false;
-    }
-    int tap_at[NT][NT];
-    for (int y = 0; y < NT; y++) {
-        for (int x = 0; x < NT; x++)
-            tap_at[y][x] = -1;
-    }
-    for (int t = 0; t < ntaps; t++) {
-        const int x = (int8_t) (taps[t] & 0xff), y = (int8_t) ((taps[t] >> 8) & 0xff);
-        if (x < -6 || x > 7 || y < -6 || y > 7)
-            return false;
-        tap_at[y + 6][x + 6] = t;
-    }
-#define WN(kx, ky, t) ((double) wall[((size_t) (ky) * ncx + (kx)) * (ntaps + 1) + (t)] * \
-                       (double) wall[((size_t) (ky) * ncx + (kx)) * (ntaps + 1) + ntaps])
-    double *sx = calloc(PL_MAX(ntaps, 1), sizeof(double)), *sy = calloc(PL_MAX(ntaps, 1), sizeof(double));
-    const size_t nfx = ((size_t) W + PLH_MX_PAD - 1) / PLH_MX_PAD * PLH_MX_PAD;
-    const size_t nfy = ((size_t) H + PLH_MX_PAD - 1) / PLH_MX_PAD * PLH_MX_PAD;
-    const size_t frag_bytes = (size_t) PLH_MXD_NFRAG * 64 * 8 * sizeof(uint16_t);
-    const size_t o_dfx = frag_bytes, o_dfy = o_dfx + nfx * 4, bytes = o_dfy + nfy * 4;
-    uint8_t *blob = calloc(1, bytes);
-    if (!sx || !sy || !blob) {
-        free(sx); free(sy); free(blob);
-        return false;
-    }
-    double den = 0.0;
-    for (int c = 0; c < ncx; c++) {
-        const double d = (double) clsx[c] - 0.5;
-        den += d * d;
-        for (int t = 0; t < ntaps; t++)
-            sx[t] += d * (WN(c, c0y, t) - WN(c0x, c0y, t));
-    }
-    for (int t = 0; t < ntaps; t++)
-        sx[t] = den > 0.0 ? sx[t] / den : 0.0;
-    den = 0.0;
-    for (int c = 0; c < ncy; c++) {
-        const double d = (double) clsy[c] - 0.5;
-        den += d * d;
-        for (int t = 0; t < ntaps; t++)
-            sy[t] += d * (WN(c0x, c, t) - WN(c0x, c0y, t));
-    }
-    for (int t = 0; t < ntaps; t++)
-        sy[t] = den > 0.0 ? sy[t] / den : 0.0;
-
-    uint16_t *frag = (uint16_t *) blob;
-    const double dscale = ldexp(1.0, -PLH_MX_DSHIFT);
-    double worst = 0.0, asym = 0.0;
-    // the first source row (and, mirrored, the last) that carries a weight at all: at fcoord = 1/2
-    // rows -6 and 7 of the reference's 14 x 14 tap square lie 6.5 texels from the sample, beyond
-    // twice any radius <= 3.25 (ewa_lanczos: 6.4766) -- the kernel starts its contraction there
-    int first_row = NT / 2 - 1;
-    for (int j = 0; j < NT / 2; j++) {
-        for (int kb = 0; kb < 2; kb++) {
-            for (int l = 0; l < 64; l++) {
-                const int n = l & 15;
-                for (int e = 0; e < 8; e++) {
-                    const int i = 32 * kb + 8 * (l >> 4) + e - 2 * n;
-                    double v = 0.0, vx = 0.0, vy = 0.0;
-                    if (i >= 0 && i < NT) {
-                        const int ta = tap_at[j][i], tb = tap_at[NT - 1 - j][i];
-                        if ((ta < 0) != (tb < 0)) {
-                            free(sx); free(sy); free(blob);
-                            return false;   // (a tap list that is not symmetric: not this filter)
-                        }
-                        if (ta >= 0) {
-                            const double wa = WN(c0x, c0y, ta), wb = WN(c0x, c0y, tb);
-                            asym = PL_MAX(asym, fabs(wa - wb));
-                            v = 0.5 * (wa + wb);
-                            vx = 0.5 * (sx[ta] + sx[tb]);
-                            vy = 0.5 * (sy[ta] - sy[tb]);
-                        }
-                    }
-                    const uint16_t hi = f32_to_f16((float) v);
-                    const uint16_t lo = f32_to_f16((float) (v - (double) f16_to_f32(hi)));
-                    worst = PL_MAX(worst, fabs(v - (double) f16_to_f32(hi) - (double) f16_to_f32(lo)));
-                    if (v != 0.0 || vx != 0.0 || vy != 0.0)
-                        first_row = PL_MIN(first_row, j);
-                    const size_t f = 4 * (size_t) (2 * j + kb);
-                    frag[((f + 0) * 64 + l) * 8 + e] = hi;
-                    frag[((f + 1) * 64 + l) * 8 + e] = lo;
-                    frag[((f + 2) * 64 + l) * 8 + e] = f32_to_f16((float) (vx * dscale));
-                    frag[((f + 3) * 64 + l) * 8 + e] = f32_to_f16((float) (vy * dscale));
-                }
-            }
-        }
-    }
-#undef WN
-    free(sx);
-    free(sy);
-    if (asym > 1e-7) {
-        pl_msg(log, PL_LOG_DEBUG, "matrix-pipe downscale: weights not symmetric about the sample "
-               "point (%.2e)", asym);
-        free(blob);
-        return false;
-    }
-    float *dfx = (float *) (blob + o_dfx), *dfy = (float *) (blob + o_dfy);
-    const float up = ldexpf(1.0f, PLH_MX_DSHIFT);
-    for (int i = 0; i < W; i++)
-        dfx[i] = (colfc[i] - 0.5f) * up;
-    for (int i = 0; i < H; i++)
-        dfy[i] = (rowfc[i] - 0.5f) * up;
-
-    pl_buf_destroy(gpu, &obj->mx_blob);
-    obj->mx_blob = pl_buf_create(gpu, pl_buf_params(.size = bytes, .storable = true,
-                                                    .initial_data = blob));
-    free(blob);
-    if (!obj->mx_blob)
-        return false;
-    const char *base = pl_hip_buf_ptr(obj->mx_blob);
-    obj->mx_host = (struct plh_polar_mx) {
-        .enabled = 2,
-        .org_x = colbase[0] - 6, .org_y = rowbase[0] - 6,
-        .row_first = { first_row, 0 },
-        .bfrag = base,
-        .dfx = (const float *) (base + o_dfx), .dfy = (const float *) (base + o_dfy),
-    };
-    obj->mx_announced = false;
-    pl_msg(log, PL_LOG_DEBUG, "matrix-pipe tables for the polar pass: 2 : 1 downscale, one phase (1/2, 1/2), "
-           "per-pixel phases within %.2e: first-order terms; row symmetry %.1e, weight split error <= %.2e",
-           dev, asym, worst);
     return true;
 }
 

@@ -72,7 +72,7 @@ struct pl_shader_t {
 
     struct plh_errdiff_args *errdiff;
     struct plh_blur_args blur;  // PLH_SHADER_BLUR
-    // polar sampler state, for the launch-time phase-class setup (shader_sampling.c)
+    // polar sampler state, for the launch-time phase-class setup (polar_tables.c)
     void *polar_obj;
     // texture and rect bound by the sampling stage (sh_bind), for pass fusion
     pl_tex src_tex;

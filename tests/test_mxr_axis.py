@@ -1,4 +1,4 @@
-"""mxr_axis (csrc/host/shader_sampling.c): the geometry check behind k_polar_mxr -- is an axis of a
+"""mxr_axis (csrc/host/polar_mx_tables.c): the geometry check behind k_polar_mxr -- is an axis of a
 polar pass an exact R : G upscale (3x, 4x, 3 : 2), with which shift, origin and per-phase texel
 offsets, and how is the phase at fcoord = 0 of an odd ratio canonicalised. Host logic only (no
 GPU): the per-output base texels and fcoords are computed here the way the kernels compute them
