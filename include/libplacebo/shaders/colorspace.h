@@ -125,11 +125,16 @@ struct pl_color_map_params {
     float contrast_smoothness;
 
     bool force_tone_mapping_lut;
-    bool visualize_lut;         // unsupported (ignored)
+    // Diagnostics of the full path (a tone map or a gamut map is needed; on the matrix-only path
+    // they do nothing). visualize_lut plots the tone curve, and a slice through the gamut map at
+    // `visualize_hue` tilted by `visualize_theta` (radians), over `visualize_rect` of the output
+    // rect (in units of it; an all-zero axis = 0 .. 1).
+    bool visualize_lut;
     pl_rect2df visualize_rect;
     float visualize_hue;
     float visualize_theta;
-    bool show_clipping;         // unsupported (ignored)
+    // marks the pixels that leave the source's declared range or the gamut LUT's domain
+    bool show_clipping;
 
     // Members of older API levels, same positions as in the reference (:306-311).
     enum pl_tone_map_mode tone_mapping_mode;    // ignored (removed in v6.269)

@@ -79,7 +79,11 @@ def peak_detect_params(smoothing_period=20.0, scene_threshold_low=1.0, scene_thr
                                  percentile, black_cutoff, allow_delayed, 0.0)
 
 
-def color_map_params(tone="spline", gamut="perceptual", **kw):
+def color_map_params(tone="spline", gamut="perceptual", show_clipping=False, visualize_lut=False,
+                     visualize_rect=(0, 0, 1, 1), visualize_hue=0.0, visualize_theta=0.0, **kw):
+    """pl_color_map_params with the library's defaults. show_clipping / visualize_lut (with
+    visualize_rect = (x0, y0, x1, y1) in units of the output rect, visualize_hue and
+    visualize_theta in radians) switch on the colour map's diagnostics; any other member by name."""
     p = capi.ColorMapParams(
         gamut_mapping=lib().pl_find_gamut_map_function(gamut.encode()),
         gamut_constants=capi.GamutMapConstants(*capi.GAMUT_MAP_CONSTANTS),
@@ -87,7 +91,9 @@ def color_map_params(tone="spline", gamut="perceptual", **kw):
         tone_mapping_function=lib().pl_find_tone_map_function(tone.encode()),
         tone_constants=capi.ToneMapConstants(*capi.TONE_MAP_CONSTANTS),
         metadata=0, lut_size=256, contrast_smoothness=3.5,
-        visualize_rect=capi.Rect2df(0, 0, 1, 1))
+        show_clipping=show_clipping, visualize_lut=visualize_lut,
+        visualize_rect=capi.Rect2df(*visualize_rect), visualize_hue=visualize_hue,
+        visualize_theta=visualize_theta)
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -18,194 +18,7 @@
 #include "samplers.hiph"
 #include "fastepi.hiph"
 
-#define PASS_BW 64
-#define PASS_BH 4
-#ifndef PASS_ITERS
-#define PASS_ITERS 1
-#endif
-
-// pl_shader_distort (sampling.c:1174-1215): the canvas position through the inverse transform,
-// then a bilinear or bicubic fetch; `alpha_mode`: the picture's edge fades over one texel
-DEV float4_t sample_distort(const plh_sampler_args &s, const plh_distort_args &d, float cx, float cy)
-{
-    const float px = (d.m[0] * cx + d.m[1] * cy) + d.c[0];
-    const float py = (d.m[2] * cx + d.m[3] * cy) + d.c[1];
-    float4_t c = d.bicubic ? sample_bicubic(s, px, py) : tex_linear(s.src, s.address_mode, px, py);
-    if (d.alpha_mode) {
-        const float bx = smoothstep01(fminf(px, 1.0f - px) / s.pt[0]);
-        const float by = smoothstep01(fminf(py, 1.0f - py) / s.pt[1]);
-        const float border = bx * by;
-        if (d.alpha_mode == 2) {        // PL_ALPHA_PREMULTIPLIED
-            c.x *= border; c.y *= border; c.z *= border;
-        }
-        c.w *= border;
-    }
-    return c;
-}
-
-DEV float4_t run_sampler(const plh_sampler_args &s, float px, float py)
-{
-    float4_t c = {0.0f, 0.0f, 0.0f, 1.0f};
-    switch (s.type) {
-    case PLH_SAMPLE_NEAREST:
-        c = scale4(tex_nearest(s.src, s.address_mode, px, py), s.scale);
-        break;
-    case PLH_SAMPLE_BILINEAR:
-        c = scale4(tex_linear(s.src, s.address_mode, px, py), s.scale);
-        break;
-    case PLH_SAMPLE_BICUBIC:
-        c = sample_bicubic(s, px, py);
-        break;
-    case PLH_SAMPLE_HERMITE:
-        c = sample_hermite(s, px, py);
-        break;
-    case PLH_SAMPLE_GAUSSIAN:
-        c = sample_gaussian(s, px, py);
-        break;
-    case PLH_SAMPLE_OVERSAMPLE:
-        c = sample_oversample(s, px, py);
-        break;
-    }
-    return c;
-}
-
-// Bilinear footprint of one output pixel (tex_linear, samplers.hiph)
-struct lin_fp { int x0, x1, y0, y1; float ax, ay; };
-
-DEV lin_fp lin_footprint(const plh_view &v, int mode, float px, float py)
-{
-    const float u = px * (float) v.w - 0.5f, w = py * (float) v.h - 0.5f;
-    const float fu = __builtin_floorf(u), fw = __builtin_floorf(w);
-    lin_fp f;
-    f.ax = u - fu; f.ay = w - fw;
-    f.x0 = plh_wrap((int) fu, v.w, mode); f.x1 = plh_wrap((int) fu + 1, v.w, mode);
-    f.y0 = plh_wrap((int) fw, v.h, mode); f.y1 = plh_wrap((int) fw + 1, v.h, mode);
-    return f;
-}
-
-/*
- * Launch shape: 64x4 lanes, each lane owns a 2x2 block of output pixels (cell), so a
- * workgroup writes 128x8 pixels and a lane stores two adjacent texels per row (16 B at
- * rgba16). Owning four pixels lets the lane
- *   - decode the recorded colour ops once for four pixels (apply_ops_n), and
- *   - for BILINEAR upscaling, fetch and decode the 2x2 source footprint once when the four
- *     pixels share it (always the case for a 2x upscale with the host-chosen cell phase):
- *     8 B/pixel through L1 instead of 32.
- * LITE: pass only uses the cheap ops (plh_ops_lite) -> smaller kernel, more waves.
- */
-// SIMPLE: the sampler is none / nearest / bilinear (the hot cases); the closed-form fast
-// samplers are only instantiated in the !SIMPLE variants, whose register budget they set.
-// CH: rows per cell (cells are 2 wide): 2x2 amortises most, 2x1 needs fewer registers
-// CUBIC: the colour map's lut3d_tricubic lookup (only this kernel carries it)
-// DOVI: the Dolby Vision reshaping / LMS ops (only this kernel carries them)
-template <bool LITE, bool SIMPLE, int CH, bool MIX = false, bool CUBIC = false, bool DOVI = false>
-__global__ __launch_bounds__(PASS_BW * PASS_BH)
-void k_pass_generic(const plh_pass p_)
-{
-    const plh_pass &p = plh_kernarg_pass();
-    const plh_sampler_args &s = p.s;
-    const int cx = blockIdx.x * PASS_BW + threadIdx.x;
-    constexpr int NPX = 2 * CH;
-    // PASS_ITERS cells per lane, PASS_BH cell rows apart: amortises the wave launch and the
-    // scalar prologue (the pass descriptor is ~2.5 KB of kernel arguments)
-#pragma unroll 1
-    for (int it = 0; it < PASS_ITERS; it++) {
-    const int cy = (blockIdx.y * PASS_ITERS + it) * PASS_BH + threadIdx.y;
-
-    float4_t c[NPX];
-    float px[NPX], py[NPX];
-#pragma unroll
-    for (int q = 0; q < NPX; q++) {
-        const int idx = 2 * cx - p.cell_padx + (q & 1), idy = CH * cy - (CH == 2 ? p.cell_pady : 0) + (q >> 1);
-        // lanes beyond the rect still run the maths in the reference and are dropped by the
-        // store guard (dispatch.c:1126-1142)
-        const float mx = p.out_scale[0] * ((float) idx + 0.5f);
-        const float my = p.out_scale[1] * ((float) idy + 0.5f);
-        px[q] = plh_attr(s.pos, 0, mx, my);
-        py[q] = plh_attr(s.pos, 1, mx, my);
-        c[q] = {0.0f, 0.0f, 0.0f, 1.0f};
-    }
-
-    switch (s.type) {
-    case PLH_SAMPLE_NONE:
-        break;
-    case PLH_SAMPLE_NEAREST: {
-        int tx[NPX], ty[NPX];
-#pragma unroll
-        for (int q = 0; q < NPX; q++) {
-            tx[q] = plh_wrap((int) __builtin_floorf(px[q] * (float) s.src.w), s.src.w, s.address_mode);
-            ty[q] = plh_wrap((int) __builtin_floorf(py[q] * (float) s.src.h), s.src.h, s.address_mode);
-        }
-        plh_fetch_n<NPX>(s.src, tx, ty, c);
-#pragma unroll
-        for (int q = 0; q < NPX; q++)
-            c[q] = scale4(c[q], s.scale);
-        break;
-    }
-    case PLH_SAMPLE_BILINEAR: {
-        lin_fp f[NPX];
-#pragma unroll
-        for (int q = 0; q < NPX; q++)
-            f[q] = lin_footprint(s.src, s.address_mode, px[q], py[q]);
-        bool shared = true;
-#pragma unroll
-        for (int q = 1; q < NPX; q++) {
-            shared = shared && f[q].x0 == f[0].x0 && f[q].x1 == f[0].x1 &&
-                     f[q].y0 == f[0].y0 && f[q].y1 == f[0].y1;
-        }
-        if (shared) {
-            const int tx[4] = { f[0].x0, f[0].x1, f[0].x0, f[0].x1 };
-            const int ty[4] = { f[0].y0, f[0].y0, f[0].y1, f[0].y1 };
-            float4_t t[4];
-            plh_fetch_n<4>(s.src, tx, ty, t);
-#pragma unroll
-            for (int q = 0; q < NPX; q++) {
-                c[q] = scale4(mix4(mix4(t[0], t[1], f[q].ax), mix4(t[2], t[3], f[q].ax), f[q].ay),
-                              s.scale);
-            }
-        } else {
-#pragma unroll
-            for (int q = 0; q < NPX; q++) {
-                const int tx[4] = { f[q].x0, f[q].x1, f[q].x0, f[q].x1 };
-                const int ty[4] = { f[q].y0, f[q].y0, f[q].y1, f[q].y1 };
-                float4_t t[4];
-                plh_fetch_n<4>(s.src, tx, ty, t);
-                c[q] = scale4(mix4(mix4(t[0], t[1], f[q].ax), mix4(t[2], t[3], f[q].ax), f[q].ay),
-                              s.scale);
-            }
-        }
-        break;
-    }
-    default:
-        if constexpr (!SIMPLE) {
-#pragma unroll
-            for (int q = 0; q < NPX; q++)
-                c[q] = s.type == PLH_SAMPLE_DISTORT ? sample_distort(s, p.distort, px[q], py[q])
-                                                    : run_sampler(s, px[q], py[q]);
-        }
-        break;
-    }
-
-    // (store coordinates and gl_FragCoord are computed only now: short live ranges keep the
-    // kernel at <= 96 VGPRs while the texel loads are in flight)
-    frag_t fcs[NPX];
-    int sx[NPX], sy[NPX];
-    bool ok[NPX];
-#pragma unroll
-    for (int q = 0; q < NPX; q++) {
-        const int idx = 2 * cx - p.cell_padx + (q & 1), idy = CH * cy - (CH == 2 ? p.cell_pady : 0) + (q >> 1);
-        fcs[q] = { (float) (idx + p.frag_x0) + 0.5f, (float) (idy + p.frag_y0) + 0.5f, 0.0f, 0,
-                   p.out_scale[0] * ((float) idx + 0.5f), p.out_scale[1] * ((float) idy + 0.5f) };
-        sx[q] = p.base_x + p.dir_x * (p.transpose ? idy : idx);
-        sy[q] = p.base_y + p.dir_y * (p.transpose ? idx : idy);
-        ok[q] = idx >= 0 && idy >= 0 && p.out_scale[0] * (float) idx < 1.0f &&
-                p.out_scale[1] * (float) idy < 1.0f && sx[q] >= 0 && sy[q] >= 0 &&
-                sx[q] < p.dst.w && sy[q] < p.dst.h;
-    }
-    apply_ops_n<NPX, false, LITE, MIX, CUBIC, DOVI>(c, p.ops, 0, p.num_ops, fcs);
-    plh_store_n<NPX>(p.dst, sx, sy, ok, c, p.nt_store);
-    }
-}
+#include "k_pass_generic.hiph"
 
 
 /* ------------------------------------------------------------------------ */
@@ -1651,6 +1464,9 @@ int plh_launch_deband(hipStream_t stream, const plh_pass *pass);
 int plh_launch_peak(hipStream_t stream, const plh_pass *pass);
 extern "C" int plh_launch_deinterlace(plh_stream stream, const struct plh_pass *pass);
 
+// k_pass_viz.hip: the variant with the colour map's diagnostics (and the Dolby Vision ops)
+int plh_launch_generic_viz(hipStream_t stream, const plh_pass *pass, bool cubic);
+
 // the generic kernel (any sampler without a kernel of its own, any op list)
 static int plh_launch_generic(hipStream_t stream, const plh_pass *pass, bool cubic, bool dovi)
 {
@@ -1732,17 +1548,23 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
     // specialised kernel, and is refused behind a sampler that has its own kernel
     // (the corner-rounding op lives in the same variant and takes the same way: no specialised
     // kernel carries it, so none may be handed a pass with it -- it would be dropped)
-    bool dovi = false;
-    for (int i = 0; i < pass->num_ops; i++)
-        dovi |= pass->ops[i].kind == PLH_OP_DOVI_RESHAPE || pass->ops[i].kind == PLH_OP_DOVI_LMS ||
-                pass->ops[i].kind == PLH_OP_CORNER_ROUND;
+    // The colour map's diagnostics (show_clipping, visualize_lut) take the same way, to a
+    // sibling of that variant with the clip flags' register (k_pass_viz.hip), which also has the
+    // tricubic lookup: the plot goes through the pixel's own LUT.
+    bool dovi = false, viz = false;
+    for (int i = 0; i < pass->num_ops; i++) {
+        dovi |= plh_op_generic_only(pass->ops[i].kind);
+        viz |= plh_op_is_viz(pass->ops[i].kind);
+    }
     if (dovi) {
         for (int i = 0; i < pass->num_ops; i++) {
-            if (pass->ops[i].kind == PLH_OP_PEAK_DETECT)
+            if (pass->ops[i].kind == PLH_OP_PEAK_DETECT || (viz && pass->ops[i].kind == PLH_OP_MIX_ADD))
                 return -1004;
         }
         if (pass->s.type >= PLH_SAMPLE_POLAR && pass->s.type != PLH_SAMPLE_DISTORT)
             return -1004;
+        if (viz)
+            return pass->num_pre_ops ? -1004 : plh_launch_generic_viz(stream, pass, cubic);
         return plh_launch_generic(stream, pass, cubic, true);
     }
 

@@ -268,7 +268,43 @@ enum plh_op_kind {
     // 2: color *= border. Like the Dolby Vision ops only in the generic kernel's DOVI variant,
     // which plh_launch_pass sends every pass that carries it to.
     PLH_OP_CORNER_ROUND,
+    // pl_color_map_params.show_clipping / visualize_lut (colorspace.c:1409-1581, :1805-1816,
+    // :1972-1981, :1997-2017): the colour map's diagnostics, only in the generic kernel's VIZ
+    // variant (the DOVI variant + one flag register per pixel), which plh_launch_pass sends every
+    // pass that carries one of them to.
+    // clip_hi / clip_lo of the pixel, collected over three stages. i0 = stage:
+    //   0 (in front of RGB2IPT): flags = any(rgb > f[0]), any(rgb < f[1])
+    //   1 (behind it):           flags |= I > f[0], I < f[1]
+    //   2 (in front of GAMUT_LUT, f[0..2] = that op's): flags |= any(idx > 1), any(idx < 0)
+    PLH_OP_CLIP_TEST,
+    // behind IPT2RGB: clip_hi paints the pixel's inverted saturation towards red, clip_lo blends
+    // it half way to (0, 0.3, 0.3)
+    PLH_OP_CLIP_MARK,
+    // behind GAMUT_LUT (op i - i0): where the plot position is inside [0, 1]^2 the pixel's IPT is
+    // replaced by a slice through the gamut map, shaded by where it lies and with the three line
+    // families on top. pos = the output rect mapped onto f[0], f[1] (x) and f[2], f[3] (y);
+    // synthetic colour = (f[4], 0, 0) + (pos.y - 1/2) * f[5..7] + (pos.x - 1/2) * f[8..10];
+    // f[11] = hue; f[12], f[13] = the iso-luminance / iso-hue lines' weights; f[14], f[15] = the
+    // LUT's luminance range (PQ). Followed by its two constant carriers:
+    PLH_OP_VIZ_GAMUT,
+    PLH_OP_VIZ_GAMUT_SRC,   // f[0..8] = LMS -> source gamut; f[9], f[10] = rgbmin, rgbmax;
+                            // f[11..14] = 1/m2, c3, 1/m1, 10000/203
+    PLH_OP_VIZ_GAMUT_DST,   // f[0..8] = LMS -> (clipped) target gamut
+    // behind CLIP_MARK: the tone curve of TONE_MAP (op i - i0), plotted over the same rect
+    // (f[0..3]); f[4..8] = input min, max, avg, output min, max (PQ); f[9] = alpha
+    PLH_OP_VIZ_TONE,
 };
+
+// the ops that exist in the generic pass kernel's DOVI / VIZ variants only
+static inline int plh_op_is_viz(int kind)
+{
+    return kind >= PLH_OP_CLIP_TEST && kind <= PLH_OP_VIZ_TONE;
+}
+static inline int plh_op_generic_only(int kind)
+{
+    return kind == PLH_OP_DOVI_RESHAPE || kind == PLH_OP_DOVI_LMS || kind == PLH_OP_CORNER_ROUND ||
+           plh_op_is_viz(kind);
+}
 
 // pl_reshape_data as the reshaping stage reads it (pl_shader_dovi_reshape packs the same)
 struct plh_dovi_comp {

@@ -9,6 +9,7 @@
  * build (oracle/_ref) and to tests/colormap_ref.py::resolve, for every tone / gamut function.
  */
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 
 #include <libplacebo/shaders/colorspace.h>
@@ -120,9 +121,60 @@ void plh_colormap_resolve(struct plh_colormap_plan *plan, const struct pl_color_
                             plan->gamut.function == &pl_gamut_map_saturation;
     if (plan->fold_saturation)
         plan->need_gamut = false;
+
+    // The diagnostics act on the full path only, each plot where the stage it shows exists
+    // (reference :1805, :1977, :2014); on the matrix-only path they do nothing.
+    if (plan->need_tone || plan->need_gamut) {
+        struct plh_colormap_viz *viz = &plan->viz;
+        viz->show_clipping = par->show_clipping;
+        viz->plot_tone = par->visualize_lut && plan->need_tone;
+        viz->plot_gamut = par->visualize_lut && plan->need_gamut;
+        if (par->visualize_lut) {
+            viz->rect = par->visualize_rect;
+            if (!viz->rect.x0 && !viz->rect.x1)
+                viz->rect.x1 = 1.0f;
+            if (!viz->rect.y0 && !viz->rect.y1)
+                viz->rect.y1 = 1.0f;
+            viz->hue = par->visualize_hue;
+            viz->theta = par->visualize_theta;
+        }
+    }
 }
 
-// for tests/test_colormap_plan.py
+int plh_colormap_op_kinds(const struct plh_colormap_plan *plan, int *kinds)
+{
+    if (plan->identity || (!plan->need_tone && !plan->need_gamut))
+        return 0;
+    const struct plh_colormap_viz *viz = &plan->viz;
+    int n = 0;
+    // the RGB test reads the colour RGB2IPT overwrites, the I test the one it leaves
+    if (viz->show_clipping)
+        kinds[n++] = PLH_OP_CLIP_TEST;
+    kinds[n++] = PLH_OP_RGB2IPT;
+    if (viz->show_clipping)
+        kinds[n++] = PLH_OP_CLIP_TEST;
+    if (plan->need_tone)
+        kinds[n++] = PLH_OP_TONE_MAP;
+    if (plan->need_gamut) {
+        if (viz->show_clipping)
+            kinds[n++] = PLH_OP_CLIP_TEST;
+        kinds[n++] = PLH_OP_GAMUT_LUT;
+        if (viz->plot_gamut) {
+            kinds[n++] = PLH_OP_VIZ_GAMUT;
+            kinds[n++] = PLH_OP_VIZ_GAMUT_SRC;
+            kinds[n++] = PLH_OP_VIZ_GAMUT_DST;
+        }
+    }
+    kinds[n++] = PLH_OP_IPT2RGB;
+    if (viz->show_clipping)
+        kinds[n++] = PLH_OP_CLIP_MARK;
+    if (viz->plot_tone)
+        kinds[n++] = PLH_OP_VIZ_TONE;
+    return n;
+}
+
+// for tests/test_colormap_plan.py: the plan up to its diagnostics (the test's mirror of the struct
+// ends there)
 PL_API void plh_test_colormap_resolve(struct plh_colormap_plan *plan, const struct pl_color_map_params *params,
                                       const struct pl_color_space *src, const struct pl_color_space *dst,
                                       bool stateful);
@@ -130,5 +182,25 @@ void plh_test_colormap_resolve(struct plh_colormap_plan *plan, const struct pl_c
                                const struct pl_color_space *src, const struct pl_color_space *dst,
                                bool stateful)
 {
-    plh_colormap_resolve(plan, params, src, dst, stateful);
+    struct plh_colormap_plan full;
+    plh_colormap_resolve(&full, params, src, dst, stateful);
+    memcpy(plan, &full, offsetof(struct plh_colormap_plan, viz));
+}
+
+// for tests/test_colormap_viz_plan.py: the diagnostics' part of the plan, as { show_clipping,
+// plot_tone, plot_gamut } and { rect x0 y0 x1 y1, hue, theta }, and the op kinds of the full path
+PL_API int plh_test_colormap_viz(const struct pl_color_map_params *params,
+                                 const struct pl_color_space *src, const struct pl_color_space *dst,
+                                 bool stateful, int flags[3], float fields[6], int *kinds);
+int plh_test_colormap_viz(const struct pl_color_map_params *params,
+                          const struct pl_color_space *src, const struct pl_color_space *dst,
+                          bool stateful, int flags[3], float fields[6], int *kinds)
+{
+    struct plh_colormap_plan plan;
+    plh_colormap_resolve(&plan, params, src, dst, stateful);
+    const struct plh_colormap_viz *viz = &plan.viz;
+    flags[0] = viz->show_clipping; flags[1] = viz->plot_tone; flags[2] = viz->plot_gamut;
+    fields[0] = viz->rect.x0; fields[1] = viz->rect.y0; fields[2] = viz->rect.x1; fields[3] = viz->rect.y1;
+    fields[4] = viz->hue; fields[5] = viz->theta;
+    return plh_colormap_op_kinds(&plan, kinds);
 }

@@ -131,6 +131,11 @@ static uint64_t digest_params(const struct pl_render_params *p)
         MIX_VALUE(&acc, c->contrast_recovery);
         MIX_VALUE(&acc, c->contrast_smoothness);
         MIX_VALUE(&acc, c->force_tone_mapping_lut);
+        MIX_VALUE(&acc, c->show_clipping);
+        MIX_VALUE(&acc, c->visualize_lut);
+        MIX_VALUE(&acc, c->visualize_rect);
+        MIX_VALUE(&acc, c->visualize_hue);
+        MIX_VALUE(&acc, c->visualize_theta);
         MIX_VALUE(&acc, c->tone_mapping_param);
         MIX_VALUE(&acc, c->intent);
         MIX_VALUE(&acc, c->gamut_mode););

@@ -187,7 +187,12 @@ void plh_draw_overlays(struct frame_job *job, pl_tex fbo, int comps, const int c
         struct pl_color_space ol_color = ol.color, target_color = target->color;
         pl_color_space_infer_map(&ol_color, &target_color);
         if (image && pl_color_space_equal(&ol_color, &image->color)) {
-            pl_shader_color_map_ex(sh, job->params->color_map_params, pl_color_map_args(
+            // (without the colour map's diagnostics: their ops exist in the generic pass kernel
+            // only, and the marks are about the image -- an overlay is drawn unmarked)
+            struct pl_color_map_params plain = *PL_DEF(job->params->color_map_params,
+                                                       &pl_color_map_default_params);
+            plain.show_clipping = plain.visualize_lut = false;
+            pl_shader_color_map_ex(sh, &plain, pl_color_map_args(
                 .src   = ol_color,
                 .dst   = color,
                 .state = &rr->tone_map_state,

@@ -1131,9 +1131,9 @@ static bool owns_workgroup_shape(const pl_shader sh)
         return true;
     // ... and so do the Dolby Vision ops: one variant of the generic kernel, without the
     // measurement's workgroup state
+    // (... and the colour map's diagnostics, in its sibling)
     for (int i = 0; i < sh->pass.num_ops; i++) {
-        if (sh->pass.ops[i].kind == PLH_OP_DOVI_RESHAPE || sh->pass.ops[i].kind == PLH_OP_DOVI_LMS ||
-            sh->pass.ops[i].kind == PLH_OP_CORNER_ROUND)
+        if (plh_op_generic_only(sh->pass.ops[i].kind))
             return true;
     }
     return false;
@@ -1401,6 +1401,15 @@ static bool apply_params_lut(struct frame_job *job, pl_shader sh, bool *prelinea
     return true;
 }
 
+static bool generic_can_run(const struct frame_job *job, const pl_shader sh);
+
+// pl_color_map_params.show_clipping / .visualize_lut: the ops they record exist in one variant of
+// the generic pass kernel only (plh_device.h)
+static bool wants_diagnostics(const struct pl_color_map_params *cm)
+{
+    return cm && (cm->show_clipping || cm->visualize_lut);
+}
+
 void plh_stage_colors(struct frame_job *job)
 {
     pl_renderer rr = job->rr;
@@ -1443,6 +1452,20 @@ void plh_stage_colors(struct frame_job *job)
         if (job->peak_pending && !plh_work_texture(job, img))
             return;
         pl_tex features = make_feature_map(job);
+        // the diagnostics go where the generic kernel's variant for them can run: a pending pass
+        // it cannot (a scaler with a kernel of its own, a measurement) is stored first, as for
+        // rounded corners. (Whether the request reaches the full path at all is the plan's
+        // decision, taken inside: on the matrix-only path this costs an intermediate for nothing,
+        // on a path nobody measures.)
+        // Stored unrounded (rgba32f), like a Dolby Vision plane: what lies outside the plot is then
+        // the frame the pass would have rendered itself, not that frame through an f16 rounding.
+        if (wants_diagnostics(cm) && img->rec && !generic_can_run(job, img->rec) && job->caps.fbo[4]) {
+            pl_fmt exact = pl_find_named_fmt(rr->gpu, "rgba32f");
+            if (exact && (exact->caps & PL_FMT_CAP_STORABLE))
+                img->store_as = exact;
+            if (!plh_work_texture(job, img))
+                return;
+        }
         sh = plh_work_shader(job, img);
         pl_shader_color_map_ex(sh, params->color_map_params, pl_color_map_args(
             .src           = image->color,

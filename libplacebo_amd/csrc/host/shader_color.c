@@ -1071,6 +1071,66 @@ static pl_buf make_gamut_lut(pl_shader sh, const struct pl_gamut_map_params *gam
     return buf;
 }
 
+/* ---- the colour map's diagnostics (pl_color_map_params.show_clipping, .visualize_lut) ---- */
+#define CLIP_EPS 1e-6f
+
+// rect_pos (:1409-1422): the attribute over the pass's output rect that is 0 .. 1 across `rc`
+// (itself in units of that rect), y running upwards: f[0], f[1] = its value at the left / right
+// edge, f[2], f[3] = at the top / bottom edge
+static void plot_position(float f[4], pl_rect2df rc)
+{
+    f[0] = -rc.x0 / (rc.x1 - rc.x0);
+    f[1] = (1.0f - rc.x0) / (rc.x1 - rc.x0);
+    f[2] = -rc.y1 / (rc.y0 - rc.y1);
+    f[3] = (1.0f - rc.y1) / (rc.y0 - rc.y1);
+}
+
+// visualize_gamut_map (:1485-1581): everything of it that does not depend on the pixel is worked
+// out here, in single precision like the shader's constant expressions
+static bool record_gamut_plot(pl_shader sh, const struct plh_colormap_viz *viz,
+                              const struct pl_gamut_map_params *gamut)
+{
+    sh_describef(sh, "gamut map plot");
+    struct plh_op *op = sh_op(sh, PLH_OP_VIZ_GAMUT);
+    if (!op)
+        return false;
+    op->i0 = 1;     // (right behind its GAMUT_LUT)
+    plot_position(op->f, viz->rect);
+    const float sn = sinf(viz->hue), ch = cosf(viz->hue);
+    const float st = sinf(viz->theta), ct = cosf(viz->theta);
+    const float mid = gamut->min_luma + (gamut->max_luma - gamut->min_luma) * 0.6f;
+    op->f[4] = 0.5f + (mid - 0.5f) * st;    // base.x = mix(0.5, mid, sin(theta))
+    // rot1 * rot2 (hue about I, after theta about P), columns 0 and 1: dir.z = 0
+    op->f[5] = ct;   op->f[6] = -sn * st;  op->f[7] = ch * st;
+    op->f[8] = 0.0f; op->f[9] = ch;        op->f[10] = sn;
+    op->f[11] = viz->hue;
+    op->f[12] = smoothstepf(0.1f, 0.0f, fabsf(st));
+    op->f[13] = smoothstepf(0.3f, 0.0f, fabsf(ct));
+    op->f[14] = gamut->min_luma;
+    op->f[15] = gamut->max_luma;
+    sh_listf(sh, "viz_gamut(rect %g %g %g %g, hue %g, theta %g)\n", viz->rect.x0, viz->rect.y0,
+             viz->rect.x1, viz->rect.y1, viz->hue, viz->theta);
+
+    if (!(op = sh_op(sh, PLH_OP_VIZ_GAMUT_SRC)))
+        return false;
+    const pl_matrix3x3 to_src = pl_ipt_lms2rgb(&gamut->input_gamut);
+    mat_to_f(op->f, &to_src);
+    op->f[9] = pl_hdr_rescale(PL_HDR_PQ, PL_HDR_NORM, gamut->min_luma);
+    op->f[10] = pl_hdr_rescale(PL_HDR_PQ, PL_HDR_NORM, gamut->max_luma);
+    op->f[11] = 1.0f / plh_fmtf(PQ_M2);
+    op->f[12] = plh_fmtf(PQ_C3);
+    op->f[13] = 1.0f / plh_fmtf(PQ_M1);
+    op->f[14] = plh_fmtf(10000 / PL_COLOR_SDR_WHITE);
+    sh_listf(sh, "viz_gamut_src(rgb in %g .. %g)\n", op->f[9], op->f[10]);
+
+    if (!(op = sh_op(sh, PLH_OP_VIZ_GAMUT_DST)))
+        return false;
+    const pl_matrix3x3 to_dst = pl_ipt_lms2rgb(&gamut->output_gamut);
+    mat_to_f(op->f, &to_dst);
+    sh_listf(sh, "viz_gamut_dst()\n");
+    return true;
+}
+
 void pl_shader_color_map_ex(pl_shader sh, const struct pl_color_map_params *params,
                             const struct pl_color_map_args *args)
 {
@@ -1129,7 +1189,20 @@ void pl_shader_color_map_ex(pl_shader sh, const struct pl_color_map_params *para
     }
 
     // ---- full path through IPT ------------------------------------------------------
-    struct plh_op *op = sh_op(sh, PLH_OP_RGB2IPT);
+    const struct plh_colormap_viz *viz = &plan.viz;
+    const int first_op = sh->pass.num_ops;
+    struct plh_op *op;
+    if (viz->show_clipping) {
+        // (:1805-1816) RGB2IPT overwrites the colour: the RGB test in front of it, the I test behind
+        sh_describef(sh, "clipping marks");
+        if (!(op = sh_op(sh, PLH_OP_CLIP_TEST)))
+            return;
+        op->i0 = 0;
+        op->f[0] = pl_hdr_rescale(PL_HDR_PQ, PL_HDR_NORM, tone.input_max) + CLIP_EPS;
+        op->f[1] = pl_hdr_rescale(PL_HDR_PQ, PL_HDR_NORM, tone.input_min) - CLIP_EPS;
+        sh_listf(sh, "clip_test(rgb > %g, rgb < %g)\n", op->f[0], op->f[1]);
+    }
+    op = sh_op(sh, PLH_OP_RGB2IPT);
     if (!op)
         return;
     mat_to_f(op->f, &rgb2lms);
@@ -1137,7 +1210,16 @@ void pl_shader_color_map_ex(pl_shader sh, const struct pl_color_map_params *para
     op->f[10] = plh_fmtf(PQ_M1); op->f[11] = plh_fmtf(PQ_C1); op->f[12] = plh_fmtf(PQ_C2);
     op->f[13] = plh_fmtf(PQ_C3); op->f[14] = plh_fmtf(PQ_M2);
     sh_listf(sh, "rgb2ipt()\n");
+    if (viz->show_clipping) {
+        if (!(op = sh_op(sh, PLH_OP_CLIP_TEST)))
+            return;
+        op->i0 = 1;
+        op->f[0] = tone.input_max + CLIP_EPS;
+        op->f[1] = tone.input_min - CLIP_EPS;
+        sh_listf(sh, "clip_test(I > %g, I < %g)\n", op->f[0], op->f[1]);
+    }
 
+    int tone_at = -1;
     if (need_tone_map) {
         const struct pl_tone_map_function *fun = tone.function;
         sh_describef(sh, "%s tone map (%.0f -> %.0f)", fun->name,
@@ -1147,6 +1229,7 @@ void pl_shader_color_map_ex(pl_shader sh, const struct pl_color_map_params *para
         op = sh_op(sh, PLH_OP_TONE_MAP);
         if (!op)
             return;
+        tone_at = sh->pass.num_ops - 1;
         if (fun == &pl_tone_map_clip && can_fast) {
             op->i0 = 0;
             op->f[0] = tone.input_min;
@@ -1240,10 +1323,20 @@ void pl_shader_color_map_ex(pl_shader sh, const struct pl_color_map_params *para
             return;
         }
 
+        const float lut_range = gamut.max_luma - gamut.min_luma;
+        if (viz->show_clipping) {
+            // (:1972-1975) the LUT's index of the pixel, as the lookup behind computes it
+            if (!(op = sh_op(sh, PLH_OP_CLIP_TEST)))
+                return;
+            op->i0 = 2;
+            op->f[0] = 1.0f / lut_range;
+            op->f[1] = -gamut.min_luma / lut_range;
+            op->f[2] = plh_fmtf(0.5f / M_PI);
+            sh_listf(sh, "clip_test(gamut LUT index outside 0 .. 1)\n");
+        }
         op = sh_op(sh, PLH_OP_GAMUT_LUT);
         if (!op)
             return;
-        const float lut_range = gamut.max_luma - gamut.min_luma;
         op->i0 = gamut.lut_size_I;
         op->i1 = gamut.lut_size_C;
         op->i2 = gamut.lut_size_h;
@@ -1258,6 +1351,8 @@ void pl_shader_color_map_ex(pl_shader sh, const struct pl_color_map_params *para
         op->ptr = pl_hip_buf_ptr(obj->gamut.lut);
         sh_listf(sh, "gamut_lut(%s, %dx%dx%d%s)\n", gamut.function->name, op->i0, op->i1, op->i2,
                  params->lut3d_tricubic ? ", tricubic" : "");
+        if (viz->plot_gamut && !record_gamut_plot(sh, viz, &gamut))
+            return;
     }
 
     op = sh_op(sh, PLH_OP_IPT2RGB);
@@ -1271,6 +1366,37 @@ void pl_shader_color_map_ex(pl_shader sh, const struct pl_color_map_params *para
     sh_listf(sh, "ipt2rgb()\n");
     if (args->state)
         sh_hold(sh, *args->state);
+
+    if (viz->show_clipping) {
+        // (:1997-2011)
+        if (!(op = sh_op(sh, PLH_OP_CLIP_MARK)))
+            return;
+        sh_listf(sh, "clip_mark()\n");
+    }
+    if (viz->plot_tone) {
+        // (:2013-2017, visualize_tone_map :1424-1483) the curve is the TONE_MAP op's own
+        sh_describef(sh, "tone map plot");
+        if (!(op = sh_op(sh, PLH_OP_VIZ_TONE)))
+            return;
+        op->i0 = sh->pass.num_ops - 1 - tone_at;
+        plot_position(op->f, viz->rect);
+        op->f[4] = tone.input_min; op->f[5] = tone.input_max; op->f[6] = tone.input_avg;
+        op->f[7] = tone.output_min; op->f[8] = tone.output_max;
+        op->f[9] = 0.8f * (need_gamut_map ? powf(cosf(viz->theta), 5.0f) : 1.0f);
+        sh_listf(sh, "viz_tone(rect %g %g %g %g, alpha %g)\n", viz->rect.x0, viz->rect.y0,
+                 viz->rect.x1, viz->rect.y1, op->f[9]);
+    }
+
+    // what was recorded is what the plan lists (colormap_plan.c: tests hold the list itself)
+    int kinds[PLH_MAX_OPS];
+    const int num_kinds = plh_colormap_op_kinds(&plan, kinds);
+    bool as_planned = sh->pass.num_ops - first_op == num_kinds;
+    for (int i = 0; as_planned && i < num_kinds; i++)
+        as_planned = sh->pass.ops[first_op + i].kind == kinds[i];
+    if (!as_planned) {
+        SH_FAIL(sh, "pl_shader_color_map_ex: the recorded ops are not the plan's");
+        return;
+    }
 
 done:
     pl_shader_delinearize(sh, &dst);

@@ -454,6 +454,26 @@ static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
 
 /* ---- PASS A fusion ------------------------------------------------------------------------------ */
 
+// an op that may run per source texel in the polar kernels' tile staging: not position
+// dependent, and not one that lives in a kernel of its own (the Dolby Vision ops, rounded
+// corners, the colour map's diagnostics: plh_op_generic_only)
+static bool polar_fusable_op(int kind)
+{
+    return kind != PLH_OP_DITHER && kind != PLH_OP_PEAK_DETECT && kind != PLH_OP_PLANE_FETCH &&
+           !plh_op_generic_only(kind);
+}
+
+// for tests/test_colormap_viz_plan.py
+PL_API int plh_test_polar_fusable_ops(const int *kinds, int n);
+int plh_test_polar_fusable_ops(const int *kinds, int n)
+{
+    for (int i = 0; i < n; i++) {
+        if (!polar_fusable_op(kinds[i]))
+            return 0;
+    }
+    return 1;
+}
+
 bool plh_shader_sample_polar_fused(pl_shader sh, const pl_shader pre,
                                    const struct pl_sample_src *src,
                                    const struct pl_sample_filter_params *params)
@@ -478,10 +498,8 @@ bool plh_shader_sample_polar_fused(pl_shader sh, const pl_shader pre,
     if (pp->num_pre_ops || pp->num_ops + scaled > PLH_MAX_OPS - 6)
         return false;
     for (int i = 0; i < pp->num_ops; i++) {
-        if (pp->ops[i].kind == PLH_OP_DITHER || pp->ops[i].kind == PLH_OP_PEAK_DETECT ||
-            pp->ops[i].kind == PLH_OP_PLANE_FETCH || pp->ops[i].kind == PLH_OP_DOVI_RESHAPE ||
-            pp->ops[i].kind == PLH_OP_DOVI_LMS || pp->ops[i].kind == PLH_OP_CORNER_ROUND)
-            return false; // position dependent / needs its own kernel
+        if (!polar_fusable_op(pp->ops[i].kind))
+            return false;
     }
 
     struct pl_sample_src fsrc = *src;

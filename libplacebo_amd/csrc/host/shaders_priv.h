@@ -117,7 +117,18 @@ struct plh_colormap_plan {
     bool need_tone, need_gamut;         // steps that remain (need_gamut false when folded)
     bool tone_direct;                   // clip / linear evaluated without a LUT
     bool fold_saturation;               // `saturation` gamut step folded into the output matrix
+    // the diagnostics (full path only; all unset on the matrix-only path and for equal spaces)
+    struct plh_colormap_viz {
+        bool show_clipping;
+        bool plot_tone, plot_gamut;     // visualize_lut, where the stage it plots exists
+        pl_rect2df rect;                // visualize_rect, an all-zero axis read as 0 .. 1
+        float hue, theta;
+    } viz;
 };
+// The op kinds the full path records for `plan`, RGB2IPT .. the last op in front of the
+// delinearisation, in order (at most PLH_MAX_OPS); 0 where the plan has no full path.
+// pl_shader_color_map_ex records exactly this list.
+int plh_colormap_op_kinds(const struct plh_colormap_plan *plan, int *kinds);
 void plh_colormap_resolve(struct plh_colormap_plan *plan, const struct pl_color_map_params *params,
                                  const struct pl_color_space *src, const struct pl_color_space *dst,
                                  bool stateful);
