@@ -194,15 +194,16 @@ struct pl_fmt_t {
     enum pl_fmt_caps caps;
     int num_components;
     int component_depth[4];
-    size_t internal_size;
+    size_t internal_size;          // bytes of a texel in device memory (!= texel_size if emulated)
     struct pl_fmt_plane planes[4]; // no planar formats here: planes[0] = the format itself
     int num_planes;                // always 1
     bool opaque;
-    bool emulated;
-    size_t texel_size;
-    size_t texel_align;
-    int host_bits[4];
-    int sample_order[4];
+    bool emulated;              // bgra8, rgb10a2, bgr10a2: stored as rgba8 / rgba16 (shader component
+                                // order), converted by a kernel in pl_tex_upload / pl_tex_download
+    size_t texel_size;          // bytes of a texel in host memory and in a pl_buf
+    size_t texel_align;         // row pitches and buffer offsets of transfers: a multiple of this
+    int host_bits[4];           // host component i: the next host_bits[i] bits from the LSB ...
+    int sample_order[4];        // ... and the shader's component sample_order[i]
     bool gatherable;
     const char *glsl_type;
     const char *glsl_format;

@@ -59,6 +59,8 @@ PL_API pl_hip pl_hip_get(pl_gpu gpu);
 
 // Wrap an existing device allocation (e.g. a torch tensor) as a pl_tex,
 // like pl_opengl_wrap / pl_vulkan_wrap. The memory is borrowed, not owned.
+// An emulated format (pl_fmt.emulated: bgra8, rgb10a2, bgr10a2) is refused with an error: the
+// memory would be in the format's host layout, which only the transfers convert.
 struct pl_hip_wrap_params {
     void *ptr;          // device pointer to texel (0,0)
     int width, height;
@@ -69,7 +71,9 @@ struct pl_hip_wrap_params {
 #define pl_hip_wrap_params(...) (&(struct pl_hip_wrap_params) { __VA_ARGS__ })
 PL_API pl_tex pl_hip_wrap(pl_gpu gpu, const struct pl_hip_wrap_params *params);
 
-// Device pointer / pitch of a texture created by this backend.
+// Device pointer / pitch of a texture created by this backend. For an emulated format this is
+// the STORAGE: ordered rgba8 texels for bgra8, ordered rgba16 texels (pl_fmt.internal_size = 8
+// bytes each) for rgb10a2 / bgr10a2 -- not the 32-bit words pl_tex_upload takes.
 PL_API void *pl_hip_tex_ptr(pl_tex tex, size_t *out_row_pitch);
 // Device pointer of a buffer created by this backend.
 PL_API void *pl_hip_buf_ptr(pl_buf buf);

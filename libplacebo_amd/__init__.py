@@ -30,6 +30,8 @@ _FMT_DTYPES = {
     "r16": (np.uint16, 1), "rg16": (np.uint16, 2), "rgba16": (np.uint16, 4),
     "r16hf": (np.float16, 1), "rg16hf": (np.float16, 2), "rgba16hf": (np.float16, 4),
     "r32f": (np.float32, 1), "rg32f": (np.float32, 2), "rgba32f": (np.float32, 4),
+    # emulated: the host layout. bgra8 as its four bytes, the 10-10-10-2 formats as one word
+    "bgra8": (np.uint8, 4), "rgb10a2": (np.uint32, 1), "bgr10a2": (np.uint32, 1),
 }
 
 ADDRESS_CLAMP, ADDRESS_REPEAT, ADDRESS_MIRROR = 0, 1, 2

@@ -755,6 +755,9 @@ def declare(lib):
     fn("pl_color_delinearize", None, P(ColorSpace), P(C.c_float))
     fn("pl_frame_clear_rgba", None, P(Gpu), P(Frame), P(C.c_float))
     fn("pl_frame_clear_tiles", None, P(Gpu), P(Frame), vp, C.c_int)
+    # test hooks (gpu_hip.c): a format description without a device; plh_texel.h's conversions
+    fn("plh_test_format", P(Fmt), C.c_char_p)
+    fn("plh_test_texel_convert", C.c_bool, C.c_char_p, C.c_int, vp, vp, C.c_size_t)
     return lib
 
 

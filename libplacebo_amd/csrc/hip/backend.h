@@ -76,6 +76,11 @@ int plh_event_elapsed_ns(plh_event a, plh_event b, uint64_t *ns);
 // fills the whole texture with a constant colour (pl_tex_clear_ex)
 int plh_launch_clear(plh_stream s, const struct plh_view *dst, const float color[4]);
 int plh_launch_swap_words(plh_stream s, const void *src, void *dst, size_t words, int wordsize);
+// k_texel.hip: the emulated formats' transfer pass over a w x h rect. texel_fmt: enum plh_texel_fmt
+// (plh_texel.h). pack == 0: `src` holds packed words in host layout, `dst` the texture's storage;
+// pack != 0: the other way round. Pitches in bytes; packed rows 4-byte, storage rows texel aligned.
+int plh_launch_texel_convert(plh_stream s, int texel_fmt, int pack, const void *src,
+                             size_t src_pitch, void *dst, size_t dst_pitch, int w, int h);
 // fills the whole texture with two-colour tiles (pl_frame_clear_tiles): texel (x, y) takes c0 where
 // fract((x + 1/2) * kx) < 1/2 and fract((y + 1/2) * ky) < 1/2 agree, c1 where they differ
 int plh_launch_clear_tiles(plh_stream s, const struct plh_view *dst, const float c0[4],

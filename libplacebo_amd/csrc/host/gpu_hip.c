@@ -14,6 +14,7 @@
 #include "gpu_priv.h"
 #include "shaders_priv.h"
 #include "cache_priv.h"
+#include "../hip/plh_texel.h"
 
 const struct pl_hip_params pl_hip_default_params = { PL_HIP_DEFAULTS };
 static const struct plh_gpu_fns hip_fns;
@@ -50,20 +51,52 @@ static const struct fmt_priv fmt_table[] = {
     FMT("r32f",     PL_FMT_FLOAT, 1, 32, PLH_FMT_R32F,    true,  "float", "r32f"),
     FMT("rg32f",    PL_FMT_FLOAT, 2, 32, PLH_FMT_RG32F,   true,  "vec2",  "rg32f"),
     FMT("rgba32f",  PL_FMT_FLOAT, 4, 32, PLH_FMT_RGBA32F, true,  "vec4",  "rgba32f"),
+    // Emulated (pl_fmt.emulated, as the reference does for formats a device lacks): one 32-bit
+    // word per texel on the host side, stored as an ordered texture of `plhfmt`, converted in
+    // pl_tex_upload / pl_tex_download (k_texel.hip). No kernel knows about them.
+#define EMU(nm, c, a, o0, o2, plhfmt, isz, tx) {                                            \
+    .pub = {                                                                            \
+        .name = nm, .type = PL_FMT_UNORM, .num_components = 4, .caps = CAPS_ALL,        \
+        .component_depth = { c, c, c, a }, .host_bits = { c, c, c, a },                 \
+        .sample_order = { o0, 1, o2, 3 }, .emulated = true,                             \
+        .internal_size = isz, .texel_size = 4, .texel_align = 4, .gatherable = true,    \
+        .glsl_type = "vec4",                                                            \
+    }, .plh = plhfmt, .texel = tx }
+    EMU("bgra8",    8, 8, 2, 0, PLH_FMT_RGBA8,  4, PLH_TEXEL_BGRA8),
+    EMU("rgb10a2", 10, 2, 0, 2, PLH_FMT_RGBA16, 8, PLH_TEXEL_RGB10A2),
+    EMU("bgr10a2", 10, 2, 2, 0, PLH_FMT_RGBA16, 8, PLH_TEXEL_BGR10A2),
 };
 
 #define NUM_FMTS ((int) PL_ARRAY_SIZE(fmt_table))
 
-// Same ordering rule as the reference's pl_gpu_finalize (gpu/utils.c:26-81);
-// all our formats share caps, so this reduces to "lower depth first, then name"
+// The ordering rule of the reference's pl_gpu_finalize (gpu/utils.c:26-81): non-opaque first, then
+// non-emulated, then the richer set of rendering capabilities, then per component the lower depth,
+// fewer host bits and the lower sample index, then the name
 static int cmp_fmt(const void *pa, const void *pb)
 {
     pl_fmt a = *(pl_fmt *) pa, b = *(pl_fmt *) pb;
+    if (a->opaque != b->opaque)
+        return PL_CMP(a->opaque, b->opaque);
+    if (a->emulated != b->emulated)
+        return PL_CMP(a->emulated, b->emulated);
+
+    const enum pl_fmt_caps rendering = PL_FMT_CAP_SAMPLEABLE | PL_FMT_CAP_STORABLE |
+                                       PL_FMT_CAP_LINEAR | PL_FMT_CAP_RENDERABLE |
+                                       PL_FMT_CAP_BLENDABLE | PL_FMT_CAP_BLITTABLE;
+    const enum pl_fmt_caps ca = a->caps & rendering, cb = b->caps & rendering;
+    const int na = __builtin_popcount(ca), nb = __builtin_popcount(cb);
+    if (na != nb)
+        return -PL_CMP(na, nb);     // more capabilities first
+    if (ca != cb)
+        return PL_CMP(ca, cb);      // the lower (more fundamental) bits first
+
     for (int i = 0; i < 4; i++) {
         if (a->component_depth[i] != b->component_depth[i])
-            return a->component_depth[i] < b->component_depth[i] ? -1 : 1;
+            return PL_CMP(a->component_depth[i], b->component_depth[i]);
         if (a->host_bits[i] != b->host_bits[i])
-            return a->host_bits[i] < b->host_bits[i] ? -1 : 1;
+            return PL_CMP(a->host_bits[i], b->host_bits[i]);
+        if (a->sample_order[i] != b->sample_order[i])
+            return PL_CMP(a->sample_order[i], b->sample_order[i]);
     }
     return strcmp(a->name, b->name);
 }
@@ -79,6 +112,31 @@ pl_fmt plh_test_format(const char *name)
             return &fmt_table[i].pub;
     }
     return NULL;
+}
+
+/* Test hook (tests/test_texel_formats.py): plh_texel.h's conversions on the host, the same
+ * functions the transfer kernels compile. pack == 0: `in` = `texels` words in host layout, `out` =
+ * storage texels (4 bytes each for bgra8, 4 x uint16 for the 10-bit formats); pack != 0: the way
+ * back. false = not an emulated format. */
+PL_API bool plh_test_texel_convert(const char *fmt, int pack, const void *in, void *out, size_t texels);
+bool plh_test_texel_convert(const char *fmt, int pack, const void *in, void *out, size_t texels)
+{
+    pl_fmt f = plh_test_format(fmt);
+    const int tx = f ? FMT_PRIV(f)->texel : PLH_TEXEL_NONE;
+    if (!tx)
+        return false;
+    const int bgr = tx == PLH_TEXEL_BGR10A2;
+    const uint32_t *src = in;
+    uint32_t *dst = out;
+    for (size_t i = 0; i < texels; i++) {
+        if (tx == PLH_TEXEL_BGRA8)
+            dst[i] = plh_texel_swap_rb8(src[i]);
+        else if (pack)
+            dst[i] = plh_texel_pack10(src[2 * i], src[2 * i + 1], bgr);
+        else
+            plh_texel_unpack10(src[i], bgr, &dst[2 * i], &dst[2 * i + 1]);
+    }
+    return true;
 }
 
 /* ------------------------------------------------------------------------ */
@@ -209,6 +267,7 @@ static void hip_destroy(pl_gpu gpu)
         plh_host_free(p->stage[i].host);
     }
     plh_free(p->scratch);
+    plh_free(p->texel_stage);
     if (p->own_stream)
         plh_stream_destroy(p->stream);
     free(p);
@@ -454,6 +513,8 @@ static bool hip_gpu_is_failed(pl_gpu gpu)
 /* ------------------------------------------------------------------------ */
 /* textures                                                                  */
 
+static bool hip_tex_transfer(pl_gpu gpu, const struct pl_tex_transfer_params *params, bool upload);
+
 static pl_tex hip_tex_create(pl_gpu gpu, const struct pl_tex_params *params)
 {
     struct gpu_priv *g = GPU_PRIV(gpu);
@@ -466,7 +527,8 @@ static pl_tex hip_tex_create(pl_gpu gpu, const struct pl_tex_params *params)
     t->gpu = gpu;
     t->plh_fmt = FMT_PRIV(params->format)->plh;
     const int rows = PL_MAX(params->h, 1);
-    const size_t row_bytes = (size_t) params->w * params->format->texel_size;
+    // (device addressing: internal_size; texel_size is the host's and differs for emulated formats)
+    const size_t row_bytes = (size_t) params->w * params->format->internal_size;
     t->pitch = PL_ALIGN2(row_bytes, (size_t) 256);
     t->ptr = plh_malloc(g->device, t->pitch * rows);
     t->owned = true;
@@ -477,7 +539,21 @@ static pl_tex hip_tex_create(pl_gpu gpu, const struct pl_tex_params *params)
         return NULL;
     }
 
-    if (params->initial_data) {
+    if (params->initial_data && FMT_PRIV(params->format)->texel) {
+        // host layout differs from the storage: the ordinary upload path (it returns with
+        // initial_data reusable, as below)
+        const struct pl_tex_transfer_params up = {
+            .tex = &t->tex, .rc = { 0, 0, 0, params->w, rows, 1 },
+            .row_pitch = (size_t) params->w * params->format->texel_size,
+            .ptr = (void *) params->initial_data,
+        };
+        if (!hip_tex_transfer(gpu, &up, true)) {
+            pl_msg(gpu->log, PL_LOG_ERR, "pl_tex_create: initial upload failed");
+            plh_free(t->ptr);
+            free(t);
+            return NULL;
+        }
+    } else if (params->initial_data) {
         const int err = plh_copy2d_h2d(g->stream, t->ptr, t->pitch, params->initial_data,
                                        row_bytes, row_bytes, rows);
         queued_unnumbered(g);
@@ -498,6 +574,13 @@ pl_tex pl_hip_wrap(pl_gpu gpu, const struct pl_hip_wrap_params *params)
         pl_msg(gpu->log, PL_LOG_ERR, "pl_hip_wrap: invalid parameters");
         return NULL;
     }
+    if (params->format->emulated) {
+        // the caller's memory would be in host layout, which no kernel reads
+        pl_msg(gpu->log, PL_LOG_ERR, "pl_hip_wrap: '%s' is an emulated format (stored as another "
+               "layout, converted in pl_tex_upload / pl_tex_download): device memory in its host "
+               "layout cannot be wrapped", params->format->name);
+        return NULL;
+    }
     struct tex_priv *t = calloc(1, sizeof(*t));
     if (!t)
         return NULL;
@@ -509,7 +592,7 @@ pl_tex pl_hip_wrap(pl_gpu gpu, const struct pl_hip_wrap_params *params)
     t->gpu = gpu;
     t->plh_fmt = FMT_PRIV(params->format)->plh;
     t->ptr = params->ptr;
-    t->pitch = PL_DEF(params->row_pitch, (size_t) params->width * params->format->texel_size);
+    t->pitch = PL_DEF(params->row_pitch, (size_t) params->width * params->format->internal_size);
     t->owned = false;
     return &t->tex;
 }
@@ -631,25 +714,79 @@ static void hip_tex_blit(pl_gpu gpu, const struct pl_tex_blit_params *params)
     }
 }
 
-// 2-D copy between a texture region and host memory or a buffer, on the stream
+// the staging buffer of the emulated formats' `ptr` transfers, at least `size` bytes
+static void *texel_stage(struct gpu_priv *g, size_t size)
+{
+    if (size > g->texel_stage_size) {
+        // (queued kernels may still read the old one)
+        if (g->texel_stage && sync_main(g))
+            return NULL;
+        plh_free(g->texel_stage);
+        g->texel_stage_size = 0;
+        g->texel_stage = plh_malloc(g->device, size);
+        if (g->texel_stage)
+            g->texel_stage_size = size;
+    }
+    return g->texel_stage;
+}
+
+// 2-D copy between a texture region and host memory or a buffer, on the stream. Host and buffer
+// addressing goes by the format's texel_size, device addressing by its internal_size; the two
+// differ for an emulated format, where k_texel.hip's conversion stands in for the copy.
 static bool hip_tex_transfer(pl_gpu gpu, const struct pl_tex_transfer_params *params, bool upload)
 {
     struct gpu_priv *g = GPU_PRIV(gpu);
     pl_tex tex = params->tex;
     const struct tex_priv *t = TEX_PRIV(tex);
     const pl_rect3d rc = params->rc;
+    const int texel = FMT_PRIV(tex->params.format)->texel;
     const size_t tsz = tex->params.format->texel_size;
     const size_t row_bytes = (size_t) (rc.x1 - rc.x0) * tsz;
     const size_t rows = rc.y1 - rc.y0;
     const size_t host_pitch = params->row_pitch;
-    uint8_t *dev = (uint8_t *) t->ptr + (size_t) rc.y0 * t->pitch + (size_t) rc.x0 * tsz;
+    uint8_t *dev = (uint8_t *) t->ptr + (size_t) rc.y0 * t->pitch +
+                   (size_t) rc.x0 * tex->params.format->internal_size;
+
+    if (texel && params->buf && params->buf_offset % 4) {
+        pl_msg(gpu->log, PL_LOG_ERR, "pl_tex_%s: buf_offset %zu is not a multiple of the texel "
+               "alignment of '%s' (4)", upload ? "upload" : "download", params->buf_offset,
+               tex->params.format->name);
+        return false;
+    }
 
     plh_tex_order(gpu, 0, upload ? NULL : tex, upload ? tex : NULL);
     if (params->timer)
         plh_timer_begin(gpu, params->timer, 0);
 
     int err;
-    if (params->buf) {
+    if (texel) {
+        const int w = rc.x1 - rc.x0;
+        uint8_t *packed;
+        size_t ppitch = host_pitch;
+        if (params->buf) {
+            packed = (uint8_t *) BUF_PRIV(params->buf)->ptr + params->buf_offset;
+        } else {
+            packed = texel_stage(g, row_bytes * rows);
+            ppitch = row_bytes;
+        }
+        if (!packed) {
+            err = -2;   // hipErrorOutOfMemory
+        } else if (upload) {
+            err = params->buf ? 0 : plh_copy2d_h2d(g->stream, packed, ppitch, params->ptr,
+                                                   host_pitch, row_bytes, rows);
+            if (!err)
+                err = plh_launch_texel_convert(g->stream, texel, 0, packed, ppitch, dev, t->pitch,
+                                               w, (int) rows);
+        } else {
+            err = plh_launch_texel_convert(g->stream, texel, 1, dev, t->pitch, packed, ppitch,
+                                           w, (int) rows);
+            if (!err && !params->buf)
+                err = plh_copy2d_d2h(g->stream, params->ptr, host_pitch, packed, ppitch,
+                                     row_bytes, rows);
+        }
+        if (!err && !params->buf && !params->callback)
+            err = sync_main(g);
+    } else if (params->buf) {
         uint8_t *bptr = (uint8_t *) BUF_PRIV(params->buf)->ptr + params->buf_offset;
         err = upload ? plh_copy2d_d2d(g->stream, dev, t->pitch, bptr, host_pitch, row_bytes, rows)
                      : plh_copy2d_d2d(g->stream, bptr, host_pitch, dev, t->pitch, row_bytes, rows);

@@ -14,7 +14,8 @@
 
 struct fmt_priv {
     struct pl_fmt_t pub;
-    int plh;            // enum plh_fmt
+    int plh;            // enum plh_fmt: the layout of the texture's memory
+    int texel;          // enum plh_texel_fmt (plh_texel.h): emulated, converted in the transfers
 };
 
 // The backend half of a pl_gpu, after the reference's `struct pl_gpu_fns` (src/gpu.h:36-77). The
@@ -104,6 +105,10 @@ struct gpu_priv {
     void *scratch;
     unsigned scratch_next;
     bool scratch_live[32];      // (PLH_SCRATCH_SLOTS) a recorded shader still points at the slot
+    // emulated formats, transfers through `ptr`: the caller's rows in host layout, tight, between
+    // the host copy and the conversion kernel. Grow-only; freed with the gpu.
+    void *texel_stage;
+    size_t texel_stage_size;
 };
 
 #define PLH_SCRATCH_SLOTS 32

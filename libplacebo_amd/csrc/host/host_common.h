@@ -19,6 +19,7 @@ extern "C" {
 #define PL_MAX(a, b) ((a) > (b) ? (a) : (b))
 #define PL_CLAMP(x, lo, hi) (PL_MIN(PL_MAX(x, lo), hi))
 #define PL_DEF(x, d) ((x) ? (x) : (d))
+#define PL_CMP(a, b) (((a) > (b)) - ((a) < (b)))
 #define PL_SQUARE(x) ((x) * (x))
 #define PL_ARRAY_SIZE(a) (sizeof(a) / sizeof((a)[0]))
 #define PL_ALIGN(x, a) (((x) + (a) - 1) / (a) * (a))

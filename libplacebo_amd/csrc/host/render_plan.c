@@ -245,6 +245,21 @@ void rp_layout_image(const struct pl_frame *image, struct rp_image_layout *lay)
     for (int i = 0; i < image->num_planes; i++) {
         struct rp_plane_layout *pl = &lay->planes[i];
         pl->plane = image->planes[i];
+        // component_mapping[c] is indexed by the format's host component c, which is sampled as
+        // channel sample_order[c] (:1661-1678, :1886-1890): from here on the mapping is indexed
+        // by sampled channel. The identity for every ordered format.
+        pl_fmt fmt = pl->plane.texture->params.format;
+        if (!pl_fmt_is_ordered(fmt)) {
+            const struct pl_plane *host = &image->planes[i];
+            pl->plane.components = 0;
+            for (int c = 0; c < 4; c++)
+                pl->plane.component_mapping[c] = PL_CHANNEL_NONE;
+            for (int c = 0; c < host->components; c++) {
+                const int ch = fmt->sample_order[c];
+                pl->plane.component_mapping[ch] = host->component_mapping[c];
+                pl->plane.components = PL_MAX(pl->plane.components, ch + 1);
+            }
+        }
         pl->role = rp_plane_role(&pl->plane, &image->repr);
 
         // an alpha mode of NONE hides the alpha channel wherever it lives

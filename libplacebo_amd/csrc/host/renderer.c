@@ -964,7 +964,7 @@ bool plh_stage_read(struct frame_job *job)
         pimg[i] = (struct work_image) {
             .tex = tex, .w = tex->params.w, .h = tex->params.h,
             .repr = image->repr, .color = image->color,
-            .comps = image->planes[i].components,
+            .comps = pl->plane.components,   // (by sampled channel: rp_layout_image)
             .rect = pl->rect,
         };
         deinterlace_plane(job, &pimg[i], i);
