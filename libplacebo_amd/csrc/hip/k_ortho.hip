@@ -656,6 +656,7 @@ int plh_launch_ortho(hipStream_t stream, const plh_pass *pass)
         plh_pass local = *pass;
         const int epi = ortho_fast_variant(&local);
         if (epi >= 0) {
+            plh_trace_kernel("k_ortho_fast");
             switch (local.s.src.fmt) {
             case PLH_FMT_RGBA16F: launch_ortho_fast<PLH_FMT_RGBA16F>(stream, &local, epi); break;
             case PLH_FMT_RGBA16:  launch_ortho_fast<PLH_FMT_RGBA16>(stream, &local, epi); break;
@@ -673,6 +674,7 @@ int plh_launch_ortho(hipStream_t stream, const plh_pass *pass)
     const dim3 block(ORTHO_BW, ORTHO_BH);
     const dim3 grid((pass->width + ORTHO_BW - 1) / ORTHO_BW,
                     (pass->height + ORTHO_BH - 1) / ORTHO_BH);
+    plh_trace_kernel("k_ortho");
     if (plh_ops_lite(pass, 0, pass->num_ops))
         PLH_LAUNCH_LAST(k_ortho<true>, grid, block, 0, stream, *pass);
     else

@@ -1596,6 +1596,7 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
     {
         plh_pass local = *pass;
         if (nearest_fast_ok(&local)) {
+            plh_trace_kernel("k_nearest_fast");
             const int cells_w = (local.width + local.cell_padx + 1) / 2;
             const dim3 block(BF_BW, BF_BH);
             const dim3 grid((cells_w + BF_BW - 1) / BF_BW,
@@ -1614,6 +1615,7 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
         const int iters = bilinear_fast_iters(&local);
         const bl_slot *tab = iters ? bilinear_tables(stream, &local) : nullptr;
         if (tab) {
+            plh_trace_kernel("k_bilinear_tab");
             if (local.s.src.fmt == PLH_FMT_RGBA16F)
                 launch_bilinear_tab<true>(stream, &local, tab);
             else
@@ -1622,6 +1624,7 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
             return err == hipSuccess ? 0 : -(int) err;
         }
         if (iters) {
+            plh_trace_kernel("k_bilinear_fast");
             if (local.s.src.fmt == PLH_FMT_RGBA16F)
                 launch_bilinear_fast<true>(stream, &local, iters);
             else
@@ -1635,6 +1638,7 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
         plh_pass local = *pass;
         plh_merge m;
         if (pass_merge_applies(&local, &m)) {
+            plh_trace_kernel("k_pass_merge");
             const dim3 block(PASS_BW, PASS_BH);
             const dim3 grid(((local.width + 1) / 2 + PASS_BW - 1) / PASS_BW, (local.height + PASS_BH - 1) / PASS_BH);
             if (local.dst.fmt == PLH_FMT_RGBA16F)
@@ -1650,6 +1654,7 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
         plh_pass local = *pass;
         plh_mixplan mp;
         if (pass_mix_applies(&local, &mp)) {
+            plh_trace_kernel("k_pass_mix");
             const dim3 block(PASS_BW, PASS_BH);
             const dim3 grid(((local.width + 1) / 2 + PASS_BW - 1) / PASS_BW, (local.height + PASS_BH - 1) / PASS_BH);
             if (local.dst.fmt == PLH_FMT_RGBA16F)
@@ -1662,6 +1667,7 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
     }
 
     if (pass_native_applies(pass, true)) {
+        plh_trace_kernel("k_pass_features");
         const dim3 block(PASS_BW, PASS_BH);
         const dim3 grid(((pass->width + 1) / 2 + PASS_BW - 1) / PASS_BW, (pass->height + PASS_BH - 1) / PASS_BH);
         if (pass->s.src.fmt == PLH_FMT_RGBA16F)
@@ -1675,6 +1681,8 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
     if (pass_native_applies(pass)) {
         plh_pass local = *pass;
         plh_match_map_chain(&local, true, true, true);
+        plh_trace_kernel(local.chain.enabled && (local.dst.fmt == PLH_FMT_RGBA16 || !local.chain.contrast_recovery)
+                         ? "k_pass_chain" : "k_pass_native");
         if (local.chain.enabled && local.dst.fmt == PLH_FMT_RGBA16F && !local.chain.contrast_recovery) {
             // (two pixels per lane: into the f16 intermediate the chain is short -- decode, linearize,
             // [sigmoidize] -- and the pass moves 16 bytes per pixel: 16-byte loads and stores. 4K:
@@ -1726,6 +1734,7 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
         return err == hipSuccess ? 0 : -(int) err;
     }
 
+    plh_trace_kernel("k_pass_generic");
     return plh_launch_generic(stream, pass, cubic, false);
 }
 

@@ -329,13 +329,17 @@ int plh_launch_polar(hipStream_t stream, const plh_pass *pass_in)
     const plh_pass *pass = &local;
     const dim3 block(POLAR_BW, POLAR_BH);
     const uint32_t cm = pass->s.comp_mask & 0xf;
-    if (pass->s.pp && plh_polar_mxd_applies(&local))
+    if (pass->s.pp && plh_polar_mxd_applies(&local)) {
+        plh_trace_kernel("k_polar_mxd");
         return plh_launch_polar_mxd(stream, pass);     // the 2 : 1 downscale on the matrix pipe
+    }
     if (pass->s.pp && pass->s.mx.enabled == 3) {
         // an integer upscale by 3 or 4 on the matrix pipe, where the pass has the kernel's shape
         plh_pass probe = local;
-        if (plh_polar_mxr_applies(&probe))
+        if (plh_polar_mxr_applies(&probe)) {
+            plh_trace_kernel("k_polar_mxr");
             return plh_launch_polar_mxr(stream, &probe);
+        }
     }
     if (pass->s.pp && pass->s.mx.enabled == 1 && (cm == 0x7 || cm == 0xf)) {
         // (the matrix-pipe kernel has a variant for the map chain of an HDR pass)
@@ -343,8 +347,11 @@ int plh_launch_polar(hipStream_t stream, const plh_pass *pass_in)
             plh_match_map_chain(&local, true);
         if (!local.chain.enabled)
             plh_match_fast_epilogue(&local);
-        if (plh_polar_mxp_applies(pass))
+        if (plh_polar_mxp_applies(pass)) {
+            plh_trace_kernel("k_polar_mxp");
             return plh_launch_polar_mxp(stream, pass);
+        }
+        plh_trace_kernel("k_polar_mx");
         return plh_launch_polar_mx(stream, pass);
     }
     // the phase-class kernels have a CHAIN variant for RGB / RGBA tiles (k_polar_pp.hiph)
@@ -362,6 +369,7 @@ int plh_launch_polar(hipStream_t stream, const plh_pass *pass_in)
         if (shmem > 160 * 1024)
             return -1000;
         const bool planes = cm == 0x1 || cm == 0x3;
+        plh_trace_kernel("k_polar_pp");
         if (pass->s.tile_fp32)
             return planes ? plh_launch_polar_pp_f32_c12(stream, pass, grid, block, shmem, n)
                           : plh_launch_polar_pp_f32(stream, pass, grid, block, shmem, n);
@@ -374,6 +382,7 @@ int plh_launch_polar(hipStream_t stream, const plh_pass *pass_in)
     const size_t shmem = 256 * sizeof(float2) + (size_t) pass->s.tile_w * pass->s.tile_h * px;
     if (shmem > 160 * 1024)
         return -1000; // host picks tile sizes that fit; see shader_sampling.c, polar_tables.c
+    plh_trace_kernel("k_polar");
     if (pass->s.tile_fp32)
         return launch_mask<float>(stream, pass, grid, block, shmem);
     return launch_mask<__half>(stream, pass, grid, block, shmem);

@@ -49,6 +49,11 @@ enum plh_switch_id {
 // the switch's value now, or its default (plh_switch.c)
 int plh_switch(enum plh_switch_id id);
 
+// PL_HIP_PASS_TRACE: "[plh] kernel <name>" on stderr behind the pass's own line -- which kernel the
+// launcher chose for it (tests assert it, so that a comparison of two kernels cannot pass by running
+// one of them twice)
+void plh_trace_kernel(const char *name);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 /* libplacebo-hip — the one reader of the PL_HIP_* environment switches (hip/plh_switch.h) */
 #include <errno.h>
 #include <limits.h>
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "host_common.h"
@@ -27,6 +28,12 @@ int plh_switch(enum plh_switch_id id)
 {
     bool bad;
     return switch_read(id, &bad);
+}
+
+void plh_trace_kernel(const char *name)
+{
+    if (plh_switch(PLH_SW_PASS_TRACE))
+        fprintf(stderr, "[plh] kernel %s\n", name);
 }
 
 void plh_switch_report(pl_log log)

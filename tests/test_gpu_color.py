@@ -80,6 +80,11 @@ def test_kat_transfer_roundtrip(gpu, trc):
 @pytest.mark.parametrize("trc", TRCS)
 @pytest.mark.parametrize("direction", ["linearize", "delinearize"])
 def test_transfer_vs_oracle(gpu, trc, direction):
+    """Random values against the fp32 oracle, within one 16-bit code of the output range -- and against
+    float64 (tests/transfer_f64.py) within K times the oracle's own error on the well-conditioned
+    samples, the bound tests/test_gpu_transfer_sweep.py holds over every code, the knees and the
+    out-of-range values."""
+    import transfer_f64 as t64
     csp = pl.color_space("bt2020" if trc in ("pq", "hlg") else "bt709", trc)
     pl.lib().pl_color_space_infer(C.byref(csp))
     mn, mx = nominal(csp)
@@ -96,6 +101,10 @@ def test_transfer_vs_oracle(gpu, trc, direction):
     scale = max(1.0, float(np.abs(ref[..., :3]).max()))
     tol = 1e-4 * scale if (trc == "pq" and direction == "linearize") else scale / 65535.0
     assert np.abs(got - ref).max() <= tol, np.abs(got - ref).max()
+    case = t64.Case(direction, trc, mn, mx, luma)
+    g = t64.Report([case.measure_image(src[..., :3], got)])
+    o = t64.Report([case.measure_image(src[..., :3], ref)])
+    assert g.E_well <= t64.K * max(o.E_well, o.E_ulp_well), (g.E_well, o.E_well, o.E_ulp_well)
 
 
 def test_pq_pair_error_bound_over_every_code(gpu):
