@@ -729,3 +729,74 @@ class Renderer:
     def destroy(self):
         if self.rr:
             lib().pl_renderer_destroy(C.byref(self.rr))
+
+
+# ---- options.h -------------------------------------------------------------------------------
+def option_list():
+    """pl_option_list as a list of capi.Opt (pl_option_count entries)"""
+    n = C.c_int.in_dll(lib(), "pl_option_count").value
+    return list((capi.Opt * n).in_dll(lib(), "pl_option_list"))
+
+
+class Options:
+    """A pl_options: pl_render_params with storage of its own, set from and saved to
+    "key=value,key=value" text. `params` is what Renderer.render takes."""
+
+    def __init__(self, log=None):
+        self.ptr = lib().pl_options_alloc(log)
+        if not self.ptr:
+            raise MemoryError("pl_options_alloc failed")
+
+    @property
+    def struct(self):
+        """the struct pl_options_t itself (not a copy)"""
+        return self.ptr.contents
+
+    @property
+    def params(self):
+        return self.ptr.contents.params
+
+    def reset(self, preset=None):
+        """preset: a capi.RenderParams, the name of a library preset ("default"), or None"""
+        if isinstance(preset, str):
+            preset = capi.RenderParams.in_dll(lib(), f"pl_render_{preset}_params")
+        lib().pl_options_reset(self.ptr, C.byref(preset) if preset is not None else None)
+
+    def load(self, text):
+        return lib().pl_options_load(self.ptr, text.encode())
+
+    def save(self):
+        return lib().pl_options_save(self.ptr).decode()
+
+    def set(self, key, value):
+        return lib().pl_options_set_str(self.ptr, key.encode(), str(value).encode())
+
+    def get(self, key):
+        """(address of the value inside the object, its text), or None"""
+        d = lib().pl_options_get(self.ptr, key.encode())
+        return (d.contents.value, d.contents.text.decode()) if d else None
+
+    def iterate(self):
+        """[(key, text)] of every option that differs from the empty configuration"""
+        out = []
+        cb = capi.OPT_ITERATE_CB(
+            lambda _p, d: out.append((d.contents.opt.contents.key.decode(), d.contents.text.decode())))
+        lib().pl_options_iterate(self.ptr, cb, None)
+        return out
+
+    def add_hook(self, hook):
+        lib().pl_options_add_hook(self.ptr, C.byref(hook))
+
+    def insert_hook(self, hook, idx):
+        lib().pl_options_insert_hook(self.ptr, C.byref(hook), idx)
+
+    def remove_hook_at(self, idx):
+        lib().pl_options_remove_hook_at(self.ptr, idx)
+
+    def raw(self):
+        """the bytes of the struct pl_options_t"""
+        return C.string_at(self.ptr, C.sizeof(capi.Options))
+
+    def free(self):
+        if self.ptr:
+            lib().pl_options_free(C.byref(self.ptr))

@@ -611,6 +611,43 @@ class Hook(C.Structure):
                 ("reset", C.c_void_p), ("hook", C.c_void_p), ("signature", C.c_uint64)]
 
 
+# ---- options.h ------------------------------------------------------------------------------
+class IccParams(C.Structure):  # shaders/icc.h: stored by pl_options, never used (no ICC engine)
+    _fields_ = [("intent", C.c_int), ("size_r", C.c_int), ("size_g", C.c_int), ("size_b", C.c_int),
+                ("max_luma", C.c_float), ("force_bpc", C.c_bool), ("cache", C.c_void_p),
+                ("cache_priv", C.c_void_p), ("cache_save", C.c_void_p), ("cache_load", C.c_void_p)]
+
+
+class Options(C.Structure):
+    """struct pl_options_t: the render params and the storage behind every pointer in them"""
+    _fields_ = [("params", RenderParams), ("deband_params", DebandParams),
+                ("sigmoid_params", SigmoidParams), ("color_adjustment", ColorAdjustment),
+                ("peak_detect_params", PeakDetectParams), ("color_map_params", ColorMapParams),
+                ("dither_params", DitherParams), ("icc_params", IccParams),
+                ("cone_params", ConeParams), ("blend_params", BlendParams),
+                ("deinterlace_params", DeinterlaceParams), ("distort_params", DistortParams),
+                ("upscaler", FilterConfig), ("downscaler", FilterConfig),
+                ("plane_upscaler", FilterConfig), ("plane_downscaler", FilterConfig),
+                ("frame_mixer", FilterConfig)]
+
+
+OPT_BOOL, OPT_INT, OPT_FLOAT, OPT_STRING = 0, 1, 2, 3
+
+
+class Opt(C.Structure):
+    _fields_ = [("key", C.c_char_p), ("name", C.c_char_p), ("type", C.c_int),
+                ("min", C.c_float), ("max", C.c_float), ("deprecated", C.c_bool),
+                ("preset", C.c_bool), ("priv", C.c_void_p)]
+
+
+class OptData(C.Structure):
+    _fields_ = [("opts", C.POINTER(Options)), ("opt", C.POINTER(Opt)), ("value", C.c_void_p),
+                ("text", C.c_char_p)]
+
+
+OPT_ITERATE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(OptData))
+
+
 # enum pl_hook_stage, in the order the renderer visits the stages
 HOOK_STAGES = ("RGB_INPUT", "LUMA_INPUT", "CHROMA_INPUT", "ALPHA_INPUT", "XYZ_INPUT",
                "CHROMA_SCALED", "ALPHA_SCALED", "NATIVE", "RGB", "LINEAR", "SIGMOID",
@@ -755,6 +792,18 @@ def declare(lib):
     fn("pl_color_delinearize", None, P(ColorSpace), P(C.c_float))
     fn("pl_frame_clear_rgba", None, P(Gpu), P(Frame), P(C.c_float))
     fn("pl_frame_clear_tiles", None, P(Gpu), P(Frame), vp, C.c_int)
+    fn("pl_options_alloc", P(Options), vp)
+    fn("pl_options_free", None, P(P(Options)))
+    fn("pl_options_reset", None, P(Options), P(RenderParams))
+    fn("pl_options_get", P(OptData), P(Options), C.c_char_p)
+    fn("pl_options_set_str", C.c_bool, P(Options), C.c_char_p, C.c_char_p)
+    fn("pl_options_iterate", None, P(Options), OPT_ITERATE_CB, vp)
+    fn("pl_options_save", C.c_char_p, P(Options))
+    fn("pl_options_load", C.c_bool, P(Options), C.c_char_p)
+    fn("pl_options_add_hook", None, P(Options), P(Hook))
+    fn("pl_options_insert_hook", None, P(Options), P(Hook), C.c_int)
+    fn("pl_options_remove_hook_at", None, P(Options), C.c_int)
+    fn("pl_find_option", P(Opt), C.c_char_p)
     # test hooks (gpu_hip.c): a format description without a device; plh_texel.h's conversions
     fn("plh_test_format", P(Fmt), C.c_char_p)
     fn("plh_test_texel_convert", C.c_bool, C.c_char_p, C.c_int, vp, vp, C.c_size_t)
@@ -804,4 +853,9 @@ MIRRORS_CUSTOM = {
     "struct pl_custom_shader": CustomShader, "struct pl_hook_params": HookParams,
     "struct pl_hook_res": HookRes, "union pl_var_data": VarData, "struct pl_hook_par": HookPar,
     "struct pl_hook": Hook,
+}
+
+# the same for options.h, against tests/golden/abi_layout_options.json (tests/test_options.py)
+MIRRORS_OPTIONS = {
+    "struct pl_options_t": Options, "struct pl_opt_t": Opt, "struct pl_opt_data_t": OptData,
 }

@@ -13,6 +13,7 @@ cross the C ABI to be layout-compatible with libplacebo's.
     tools/abi_probe.py ref             # table for /root/reference (needs oracle/_ref/gen)
     tools/abi_probe.py golden          # rewrite tests/golden/abi_layout.json from the reference
     tools/abi_probe.py golden-custom   # the same for shaders/custom.h -> abi_layout_custom.json
+    tools/abi_probe.py golden-options  # the same for options.h -> abi_layout_options.json
 
 Headers listed in GROUPS have a table (and a golden file) of their own: every other command and
 function looks at the main set unless told otherwise, so that a header added later does not change
@@ -40,6 +41,8 @@ OWN_HEADERS = {"libplacebo/hip.h"}
 GROUPS = {
     "custom": ({"libplacebo/shaders/custom.h"},
                os.path.join(ROOT, "tests", "golden", "abi_layout_custom.json")),
+    "options": ({"libplacebo/options.h"},
+                os.path.join(ROOT, "tests", "golden", "abi_layout_options.json")),
 }
 GROUPED_HEADERS = set().union(*(g[0] for g in GROUPS.values()))
 
@@ -68,6 +71,7 @@ def split_members(body):
 def member_names(decl):
     """Names declared by one member declaration (`int a, b[4];`, `void (*cb)(void *);`, ...)."""
     decl = re.sub(r"\{.*\}", "", decl, flags=re.S)  # anonymous/nested aggregate body
+    decl = re.sub(r"\bPL_DEPRECATED(_ENUM)?_IN\s*\([^)]*\)", "", decl)  # (may follow the name)
     m = re.search(r"\(\s*\*\s*(\w+)\s*\)\s*\(", decl)
     if m:
         return [m.group(1)]
