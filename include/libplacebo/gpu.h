@@ -65,17 +65,18 @@ struct pl_glsl_version {
 
 struct pl_gpu_limits {
     bool thread_safe;
-    bool callbacks;
+    bool callbacks;             // true: transfer callbacks are deferred (pl_tex_transfer_params)
     size_t max_buf_size;
     size_t max_ubo_size;
     size_t max_ssbo_size;
     size_t max_vbo_size;
-    size_t max_mapped_size;
+    size_t max_mapped_size;     // 0. Describes buffers the backend ALLOCATES: none of those can be
+                                // host_mapped. An imported host pointer is its own mapping.
     uint64_t max_buffer_texels;
     bool host_cached;           // host-mapped buffers are cached (pinned memory here: no)
     bool host_ptr_slow;
     size_t max_mapped_vram;
-    size_t align_host_ptr;      // 0: host pointers cannot be imported
+    size_t align_host_ptr;      // the page size: imported host pointers are rounded to it
     uint32_t max_tex_1d_dim;
     uint32_t max_tex_2d_dim;
     uint32_t max_tex_3d_dim;
@@ -96,9 +97,10 @@ struct pl_gpu_limits {
 #define max_xfer_size max_buf_size
 #define align_tex_xfer_stride align_tex_xfer_pitch
 
-// External memory handles (reference gpu.h:150-203). Nothing can be imported or exported on
-// this backend (zero-copy ingest of device memory goes through pl_hip_wrap, hip.h): all caps
-// are 0 and a non-zero handle type in a params struct is refused.
+// External memory handles (reference gpu.h:150-203). Buffers can be imported from host pointers
+// (import_caps.buf = PL_HANDLE_HOST_PTR: the caller's frames, see hip.h "Imported buffers");
+// every other cap is 0 and any other non-zero handle type in a params struct is refused.
+// Zero-copy ingest of DEVICE memory goes through pl_hip_wrap (hip.h).
 typedef uint64_t pl_handle_caps;
 enum pl_handle_type {
     PL_HANDLE_FD        = (1 << 0),
@@ -146,7 +148,7 @@ typedef const struct pl_gpu_t {
     struct pl_glsl_version glsl;
     struct pl_gpu_limits limits;
     struct pl_gpu_handle_caps export_caps;  // all 0
-    struct pl_gpu_handle_caps import_caps;  // all 0
+    struct pl_gpu_handle_caps import_caps;  // .buf = PL_HANDLE_HOST_PTR, the rest 0
     uint8_t uuid[16];
     pl_fmt *formats;            // sorted best-first, like pl_gpu_finalize does
     int num_formats;
@@ -240,15 +242,15 @@ struct pl_buf_params {
     size_t size;
     bool host_writable;
     bool host_readable;
-    bool host_mapped;
+    bool host_mapped;                   // only together with a host pointer import
     bool uniform;
     bool storable;
     bool drawable;                      // refused (no vertex input)
     enum pl_buf_mem_type memory_type;
     pl_fmt format;                      // texel buffers: refused
     enum pl_handle_type export_handle;  // refused
-    enum pl_handle_type import_handle;  // refused
-    struct pl_shared_mem shared_mem;
+    enum pl_handle_type import_handle;  // PL_HANDLE_HOST_PTR (transfer buffers only), or 0
+    struct pl_shared_mem shared_mem;    // import: handle.ptr, size of the memory, offset of the buffer
     const void *initial_data;
     void *user_data;
     pl_debug_tag debug_tag;
@@ -258,8 +260,8 @@ struct pl_buf_params {
 
 typedef const struct pl_buf_t {
     struct pl_buf_params params;
-    uint8_t *data; // host_mapped only
-    struct pl_shared_mem shared_mem;    // unused
+    uint8_t *data; // imported host pointers (the caller's pointer + offset), else NULL
+    struct pl_shared_mem shared_mem;    // imports: the page-rounded region
 } *pl_buf;
 
 PL_API pl_buf pl_buf_create(pl_gpu gpu, const struct pl_buf_params *params);
@@ -270,6 +272,9 @@ PL_API bool pl_buf_read(pl_gpu gpu, pl_buf buf, size_t buf_offset, void *dest, s
 PL_API void pl_buf_copy(pl_gpu gpu, pl_buf dst, size_t dst_offset,
                         pl_buf src, size_t src_offset, size_t size);
 PL_API bool pl_buf_export(pl_gpu gpu, pl_buf buf);   // always false (no exportable handles)
+// true = still in use. An imported buffer answers for itself: false as soon as the last transfer or
+// copy queued on IT has completed (timeout in ns; 0 asks, UINT64_MAX waits). Any other buffer is
+// in use while anything at all is queued on this pl_gpu.
 PL_API bool pl_buf_poll(pl_gpu gpu, pl_buf buf, uint64_t timeout);
 
 enum pl_tex_sample_mode {
@@ -359,6 +364,11 @@ struct pl_tex_transfer_params {
     size_t row_pitch;       // bytes between rows in host memory (0 = packed)
     size_t depth_pitch;
     pl_timer timer;
+    // Runs once the transfer has completed, on the calling thread, in order of submission; it may
+    // call back into the library. A `buf` transfer returns at once and its callback runs later:
+    // from inside the next pl_tex_upload / pl_tex_download / pl_buf_poll / pl_tex_poll /
+    // pl_gpu_flush that finds it completed, or pl_gpu_finish. A `ptr` transfer returns when `ptr`
+    // may be reused / is filled, with or without a callback, which has run by then.
     void (*callback)(void *priv);
     void *priv;
     pl_buf buf;             // device-side transfer source/target (optional)

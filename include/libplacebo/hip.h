@@ -76,6 +76,21 @@ PL_API pl_tex pl_hip_wrap(pl_gpu gpu, const struct pl_hip_wrap_params *params);
 // bytes each) for rgb10a2 / bgr10a2 -- not the 32-bit words pl_tex_upload takes.
 PL_API void *pl_hip_tex_ptr(pl_tex tex, size_t *out_row_pitch);
 // Device pointer of a buffer created by this backend.
+//
+// Imported buffers. pl_buf_create with import_handle = PL_HANDLE_HOST_PTR takes shared_mem.handle.ptr
+// (rounded to pages of limits.align_host_ptr, like the reference does) and registers those pages
+// with the HIP runtime for the life of the buffer: pl_tex_upload / pl_tex_download with such a `buf`
+// are asynchronous DMA from / into the caller's own memory and return at once; pl_buf_poll(buf)
+// says when THAT buffer's last queued transfer has completed, whatever else is queued behind it,
+// and a `callback` runs once it has (gpu.h). The memory stays the caller's: pl_buf_destroy waits
+// for the buffer's last transfer, undoes the registration and frees nothing. Registering costs
+// far more than one copy saves -- import a ring of frame buffers once and reuse it
+// ("Frame I/O"), and import one buffer per page range: a page that a live import
+// already covers cannot be counted on to register a second time (address slices of one allocation
+// with buf_offset). A download into an imported buffer runs beside the work queued behind it, on
+// a stream of the library's own (not with pl_hip_params.stream). Such a buffer is a transfer buffer only (no uniform / storable /
+// drawable / format); buf->data is the caller's pointer plus offset. For it this function returns
+// the address under which kernels on the device see that memory.
 PL_API void *pl_hip_buf_ptr(pl_buf buf);
 
 // Kernels of the caller's own on a texture of this backend (a renderer hook, shaders/custom.h):

@@ -148,10 +148,65 @@ class Texture:
             raise RuntimeError("pl_tex_download failed")
         return out
 
+    def _transfer(self, upload, buf, rect, row_pitch, buf_offset, callback):
+        xp = capi.TexTransferParams(tex=self.ptr, buf=C.cast(buf.ptr, C.c_void_p),
+                                    buf_offset=buf_offset, row_pitch=row_pitch)
+        if rect is not None:
+            x0, y0, x1, y1 = rect
+            xp.rc = capi.Rect3d(x0, y0, 0, x1, y1, 1)
+        if callback is not None:
+            xp.callback = C.cast(self.gpu.transfer_callback(callback), C.c_void_p)
+        fn = lib().pl_tex_upload if upload else lib().pl_tex_download
+        return fn(self.gpu.gpu, C.byref(xp))
+
+    def upload_from(self, buf, rect=None, row_pitch=0, buf_offset=0, callback=None):
+        """pl_tex_upload from a Buf; rect = (x0, y0, x1, y1); callback: a Python callable without
+        arguments, run by the library once the transfer has completed (deferred)"""
+        return self._transfer(True, buf, rect, row_pitch, buf_offset, callback)
+
+    def download_to(self, buf, rect=None, row_pitch=0, buf_offset=0, callback=None):
+        """pl_tex_download into a Buf (see upload_from)"""
+        return self._transfer(False, buf, rect, row_pitch, buf_offset, callback)
+
+    def poll(self, timeout=0):
+        return lib().pl_tex_poll(self.gpu.gpu, self.ptr, timeout)
+
     def destroy(self):
         if self.ptr:
             p = self.ptr
             lib().pl_tex_destroy(self.gpu.gpu, C.byref(p))
+            self.ptr = None
+
+
+POLL_FOREVER = 2 ** 64 - 1
+
+
+class Buf:
+    """A pl_buf. `array`: the numpy array an imported buffer lives in (kept alive here)."""
+
+    def __init__(self, gpu, ptr, array=None):
+        self.gpu, self.ptr, self.array = gpu, ptr, array
+
+    @property
+    def size(self):
+        return self.ptr.contents.params.size
+
+    @property
+    def data(self):
+        """buf->data (an address, or None)"""
+        return self.ptr.contents.data
+
+    def device_ptr(self):
+        return lib().pl_hip_buf_ptr(self.ptr)
+
+    def poll(self, timeout=0):
+        """pl_buf_poll: True = still in use; timeout in ns, POLL_FOREVER waits"""
+        return lib().pl_buf_poll(self.gpu.gpu, self.ptr, timeout)
+
+    def destroy(self):
+        if self.ptr:
+            p = self.ptr
+            lib().pl_buf_destroy(self.gpu.gpu, C.byref(p))
             self.ptr = None
 
 
@@ -326,6 +381,8 @@ class HipGpu:
         """async_measure: None = the library's default (pl_hip_default_params: on)"""
         L = lib()
         self._msgs = []
+        self._callbacks = {}        # transfer callbacks that have not run yet
+        self._spent, self._in_callback = [], 0
 
         def _cb(_priv, level, msg):
             self._msgs.append((level, msg.decode(errors="replace")))
@@ -372,6 +429,48 @@ class HipGpu:
         if not t:
             raise RuntimeError("pl_hip_wrap failed")
         return Texture(self, t, owned=False)
+
+    def buf_create(self, params):
+        """pl_buf_create from a capi.BufParams; None when the library refuses it"""
+        b = lib().pl_buf_create(self.gpu, C.byref(params))
+        return Buf(self, b) if b else None
+
+    def buf_import(self, array, offset=0, size=None, handle=capi.HANDLE_HOST_PTR, **flags):
+        """pl_buf_create importing the memory of a numpy array (PL_HANDLE_HOST_PTR): shared_mem =
+        the whole array, the buffer = `size` bytes at `offset` in it. flags: host_readable,
+        host_writable, host_mapped, ... (pl_buf_params members). None when refused."""
+        size = array.nbytes - offset if size is None else size
+        bp = capi.BufParams(size=size, import_handle=handle, **flags)
+        bp.shared_mem.handle = array.ctypes.data
+        bp.shared_mem.size = array.nbytes
+        bp.shared_mem.offset = offset
+        b = lib().pl_buf_create(self.gpu, C.byref(bp))
+        return Buf(self, b, array) if b else None
+
+    def transfer_callback(self, fn):
+        """a C callback running fn(); kept alive until it has run (each runs exactly once)"""
+        key = object()
+
+        def _run(_priv):
+            # (a C callback object must outlive its own call: parked, freed outside any callback)
+            self._spent.append(self._callbacks.pop(key))
+            self._in_callback += 1
+            try:
+                fn()
+            finally:
+                self._in_callback -= 1
+
+        if not self._in_callback:
+            self._spent.clear()
+        self._callbacks[key] = capi.TRANSFER_CB(_run)
+        return self._callbacks[key]
+
+    def stream_syncs(self):
+        """plh_test_stream_syncs: whole-stream drains so far"""
+        return lib().plh_test_stream_syncs(self.gpu)
+
+    def flush(self):
+        lib().pl_gpu_flush(self.gpu)
 
     def begin(self):
         return Shader(self)

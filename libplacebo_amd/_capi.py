@@ -205,6 +205,24 @@ class TexTransferParams(C.Structure):
                 ("ptr", C.c_void_p), ("no_import", C.c_bool)]
 
 
+TRANSFER_CB = C.CFUNCTYPE(None, C.c_void_p)     # pl_tex_transfer_params.callback
+
+HANDLE_FD, HANDLE_DMA_BUF, HANDLE_HOST_PTR = 1 << 0, 1 << 3, 1 << 4
+
+
+class BufParams(C.Structure):
+    _fields_ = [("size", C.c_size_t), ("host_writable", C.c_bool), ("host_readable", C.c_bool),
+                ("host_mapped", C.c_bool), ("uniform", C.c_bool), ("storable", C.c_bool),
+                ("drawable", C.c_bool), ("memory_type", C.c_int), ("format", C.POINTER(Fmt)),
+                ("export_handle", C.c_int), ("import_handle", C.c_int),
+                ("shared_mem", SharedMem), ("initial_data", C.c_void_p),
+                ("user_data", C.c_void_p), ("debug_tag", C.c_char_p)]
+
+
+class Buf(C.Structure):
+    _fields_ = [("params", BufParams), ("data", C.c_void_p), ("shared_mem", SharedMem)]
+
+
 class TexBlitParams(C.Structure):
     _fields_ = [("src", C.POINTER(Tex)), ("dst", C.POINTER(Tex)), ("src_rc", Rect3d),
                 ("dst_rc", Rect3d), ("sample_mode", C.c_int)]
@@ -807,6 +825,22 @@ def declare(lib):
     # test hooks (gpu_hip.c): a format description without a device; plh_texel.h's conversions
     fn("plh_test_format", P(Fmt), C.c_char_p)
     fn("plh_test_texel_convert", C.c_bool, C.c_char_p, C.c_int, vp, vp, C.c_size_t)
+    # frame I/O: imported buffers, polling, deferred callbacks
+    fn("pl_buf_create", P(Buf), P(Gpu), P(BufParams))
+    fn("pl_buf_destroy", None, P(Gpu), P(P(Buf)))
+    fn("pl_buf_poll", C.c_bool, P(Gpu), P(Buf), C.c_uint64)
+    fn("pl_buf_write", None, P(Gpu), P(Buf), C.c_size_t, vp, C.c_size_t)
+    fn("pl_buf_read", C.c_bool, P(Gpu), P(Buf), C.c_size_t, vp, C.c_size_t)
+    fn("pl_buf_copy", None, P(Gpu), P(Buf), C.c_size_t, P(Buf), C.c_size_t, C.c_size_t)
+    fn("pl_tex_poll", C.c_bool, P(Gpu), P(Tex), C.c_uint64)
+    fn("pl_gpu_flush", None, P(Gpu))
+    fn("pl_gpu_is_failed", C.c_bool, P(Gpu))
+    fn("pl_hip_buf_ptr", vp, P(Buf))
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "plh_test_stream_syncs"):
+        # (another build named by PL_HIP_LIB may predate these)
+        fn("plh_test_stream_syncs", C.c_uint64, P(Gpu))
+        fn("plh_test_host_ptr_round", C.c_bool, vp, C.c_size_t, C.c_size_t, C.c_size_t, P(vp),
+           P(C.c_size_t), P(C.c_size_t))
     return lib
 
 

@@ -48,6 +48,12 @@ void plh_free(void *ptr);
 void *plh_host_alloc(size_t size); // pinned
 void *plh_host_alloc_coherent(size_t size); // pinned, fine-grained, device-mapped
 void plh_host_free(void *ptr);
+// The caller's own host memory made known to the runtime (page-locked and mapped for the device):
+// copies from and to it are asynchronous DMA, and kernels reach it through `*dev_alias`. `ptr` and
+// `size` are whole pages (plh_host_ptr_round). The memory stays the caller's: plh_host_unregister
+// only undoes the registration.
+int plh_host_register(void *ptr, size_t size, void **dev_alias);
+int plh_host_unregister(void *ptr);
 
 int plh_copy2d_h2d(plh_stream s, void *dst, size_t dpitch, const void *src, size_t spitch,
                    size_t row_bytes, size_t rows);
@@ -60,6 +66,11 @@ int plh_memset(plh_stream s, void *dst, int value, size_t size);
 typedef void *plh_event;
 int plh_event_create(plh_event *out);
 void plh_event_destroy(plh_event e);
+// Fences: events without timestamps, for "has this point of a stream been reached" only (an
+// imported buffer's last use, a transfer callback). They keep the system-scope release that
+// makes a kernel's stores to host memory visible to the host once the event has completed.
+// Destroyed with plh_event_destroy; the pl_gpu keeps a small pool of them (gpu_hip.c).
+int plh_fence_create(int device, plh_event *out);
 int plh_event_record(plh_event e, plh_stream s);
 // An event for the END of the pass launched next on this thread: carried by the launch of the
 // pass's last kernel as its stop event where the launcher supports it (devmath.hiph:

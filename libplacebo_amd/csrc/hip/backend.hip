@@ -6,6 +6,7 @@
  */
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <mutex>
 
 #include "backend.h"
 #include "devmath.hiph"
@@ -179,6 +180,27 @@ void plh_host_free(void *ptr)
         (void) hipHostFree(ptr);
 }
 
+// (portable: a host thread may drive several pl_gpu objects, the current device is not
+// necessarily the one whose stream will copy)
+int plh_host_register(void *ptr, size_t size, void **dev_alias)
+{
+    CHK(hipHostRegister(ptr, size, hipHostRegisterMapped | hipHostRegisterPortable));
+    void *dev = NULL;
+    const hipError_t err = hipHostGetDevicePointer(&dev, ptr, 0);
+    if (err != hipSuccess || !dev) {
+        (void) hipHostUnregister(ptr);
+        return -(int) (err != hipSuccess ? err : hipErrorInvalidValue);
+    }
+    *dev_alias = dev;
+    return 0;
+}
+
+int plh_host_unregister(void *ptr)
+{
+    CHK(hipHostUnregister(ptr));
+    return 0;
+}
+
 int plh_copy2d_h2d(plh_stream s, void *dst, size_t dpitch, const void *src, size_t spitch,
                    size_t row_bytes, size_t rows)
 {
@@ -221,6 +243,27 @@ void plh_event_destroy(plh_event e)
 {
     if (e)
         (void) hipEventDestroy((hipEvent_t) e);
+}
+
+// ---- fences (backend.h) -------------------------------------------------------------------------
+// hipEventDisableTiming only: NOT hipEventDisableSystemFence, whose events complete without the
+// system-scope release -- a kernel's stores to registered host memory would then not be
+// guaranteed visible to the host that has seen the event complete. (plh_event_create passes no
+// flags at all: timed, with the release.)
+int plh_fence_create(int device, plh_event *out)
+{
+    int cur = device;
+    (void) hipGetDevice(&cur);
+    if (cur != device)
+        CHK(hipSetDevice(device));
+    hipEvent_t e = nullptr;
+    const hipError_t err = hipEventCreateWithFlags(&e, hipEventDisableTiming);
+    if (cur != device)
+        (void) hipSetDevice(cur);
+    if (err != hipSuccess)
+        return -(int) err;
+    *out = (plh_event) e;
+    return 0;
 }
 
 // ---- an event offered for the end of the next pass (devmath.hiph: PLH_LAUNCH_LAST) ---------------

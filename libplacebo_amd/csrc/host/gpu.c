@@ -11,11 +11,12 @@
 #include <libplacebo/hip.h>
 
 #include "gpu_priv.h"
+#include "host_ptr.h"
 #include "shaders_priv.h"
 #include "cache_priv.h"
 
 /* ------------------------------------------------------------------------ */
-/* formats                                                                   */
+/* formats                                                                  */
 
 bool pl_fmt_is_ordered(pl_fmt fmt)
 {
@@ -272,6 +273,11 @@ static bool check_tex_params(pl_gpu gpu, const struct pl_tex_params *params)
                params->w, params->h);
         return false;
     }
+    if (params->import_handle || params->export_handle) {
+        pl_msg(gpu->log, PL_LOG_ERR, "pl_tex_create: textures are neither imported nor exported "
+               "(import_caps.tex and export_caps.tex are 0; wrap device memory with pl_hip_wrap)");
+        return false;
+    }
     return true;
 }
 
@@ -457,6 +463,13 @@ bool pl_tex_poll(pl_gpu gpu, pl_tex tex, uint64_t timeout)
 /* ------------------------------------------------------------------------ */
 /* buffers                                                                   */
 
+// Test hook (tests/test_host_ptr_round.py, CPU): host_ptr.h's rounding as this file compiles it
+bool plh_test_host_ptr_round(const void *ptr, size_t offset, size_t size, size_t align,
+                             void **out_base, size_t *out_offset, size_t *out_size)
+{
+    return plh_host_ptr_round(ptr, offset, size, align, out_base, out_offset, out_size);
+}
+
 pl_buf pl_buf_create(pl_gpu gpu, const struct pl_buf_params *params)
 {
     if (!params->size || params->size > gpu->limits.max_buf_size) {
@@ -464,19 +477,72 @@ pl_buf pl_buf_create(pl_gpu gpu, const struct pl_buf_params *params)
                gpu->limits.max_buf_size);
         return NULL;
     }
-    if (params->import_handle || params->export_handle) {
-        pl_msg(gpu->log, PL_LOG_ERR, "pl_buf_create: this backend neither imports nor exports "
-               "buffer handles (wrap device memory with pl_hip_wrap instead)");
+    if (params->export_handle) {
+        pl_msg(gpu->log, PL_LOG_ERR, "pl_buf_create: this backend exports no buffer handles "
+               "(pl_hip_buf_ptr gives the device address)");
         return NULL;
     }
-    // what each use of a buffer may ask for (src/gpu.c:595-604); limits.max_mapped_size is 0 on
-    // this backend, so a host_mapped buffer is refused here instead of coming back without `data`
+    // imports: the reference's checks (src/gpu.c:552-588)
+    struct pl_buf_params rounded;
+    const bool imported = !!params->import_handle;
+    if (imported) {
+        const unsigned h = params->import_handle;
+        if (h & (h - 1)) {
+            pl_msg(gpu->log, PL_LOG_ERR, "pl_buf_create: import_handle 0x%x names more than one "
+                   "handle type", h);
+            return NULL;
+        }
+        if (!(h & gpu->import_caps.buf)) {
+            pl_msg(gpu->log, PL_LOG_ERR, "pl_buf_create: handle type 0x%x cannot be imported "
+                   "(import_caps.buf = 0x%llx: host pointers only; wrap device memory with "
+                   "pl_hip_wrap instead)", h, (unsigned long long) gpu->import_caps.buf);
+            return NULL;
+        }
+        const struct pl_shared_mem *shmem = &params->shared_mem;
+        if (shmem->offset + params->size < shmem->offset ||
+            shmem->offset + params->size > shmem->size) {
+            pl_msg(gpu->log, PL_LOG_ERR, "pl_buf_create: %zu bytes at offset %zu exceed the "
+                   "imported memory (%zu bytes)", params->size, shmem->offset, shmem->size);
+            return NULL;
+        }
+        if (params->uniform || params->storable || params->drawable || params->format) {
+            pl_msg(gpu->log, PL_LOG_ERR, "pl_buf_create: an imported buffer is a transfer buffer: "
+                   "it may be host_readable, host_writable and host_mapped, not uniform, storable, "
+                   "drawable or a texel buffer (`format`)");
+            return NULL;
+        }
+        if (h == PL_HANDLE_HOST_PTR) {
+            if (!shmem->handle.ptr) {
+                pl_msg(gpu->log, PL_LOG_ERR, "pl_buf_create: host pointer import without a pointer");
+                return NULL;
+            }
+            rounded = *params;
+            struct pl_shared_mem *r = &rounded.shared_mem;
+            if (plh_host_ptr_round(shmem->handle.ptr, shmem->offset, shmem->size,
+                                   gpu->limits.align_host_ptr, &r->handle.ptr, &r->offset, &r->size)) {
+                static bool warned_rounding = false;
+                if (!warned_rounding) {
+                    warned_rounding = true;
+                    pl_msg(gpu->log, PL_LOG_WARN, "Imported host pointer is not page-aligned. "
+                           "This should normally be fine on most platforms, but may cause issues "
+                           "in some rare circumstances.");
+                }
+                pl_msg(gpu->log, PL_LOG_TRACE, "Rounding imported host pointer %p + %zu -> %zu to "
+                       "nearest page boundaries: %p + %zu -> %zu", shmem->handle.ptr, shmem->offset,
+                       shmem->size, r->handle.ptr, r->offset, r->size);
+            }
+            params = &rounded;
+        }
+    }
+    // what each use of a buffer may ask for (src/gpu.c:595-604); limits.max_mapped_size describes
+    // buffers the backend allocates and is 0, so a plain host_mapped buffer is refused here instead
+    // of coming back without `data`. An imported host pointer IS its own mapping.
     const struct { bool wanted; size_t limit; const char *what; } uses[] = {
         { params->uniform, gpu->limits.max_ubo_size, "uniform" },
         { params->storable, gpu->limits.max_ssbo_size, "storable" },
         { params->drawable, gpu->limits.max_vbo_size, "drawable" },
-        { params->host_mapped, gpu->limits.max_mapped_size, "host_mapped" },
-        { params->host_mapped && params->memory_type == PL_BUF_MEM_DEVICE,
+        { params->host_mapped && !imported, gpu->limits.max_mapped_size, "host_mapped" },
+        { params->host_mapped && !imported && params->memory_type == PL_BUF_MEM_DEVICE,
           gpu->limits.max_mapped_vram, "host_mapped in device memory" },
     };
     for (size_t i = 0; i < PL_ARRAY_SIZE(uses); i++) {

@@ -4,10 +4,15 @@
  * src/opengl/gpu*.c). Object creation, the format table, limits, and the functions the validating
  * front-end (gpu.c) calls through. Textures are pitched linear device arrays; all work is ordered
  * on one HIP stream, so uploads / passes / downloads issued in API order execute in that order
- * without further fences.
+ * without further fences. What the HOST may touch and when is another matter: buffers imported
+ * from host pointers carry a fence of their own, and transfer callbacks wait in a queue
+ * ("transfer callbacks and fences").
  */
+#include <sched.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
+#include <unistd.h>
 
 #include <libplacebo/hip.h>
 
@@ -140,6 +145,80 @@ bool plh_test_texel_convert(const char *fmt, int pack, const void *in, void *out
 }
 
 /* ------------------------------------------------------------------------ */
+/* transfer callbacks and fences                                             */
+//
+// pl_tex_transfer_params.callback: the transfer records a fence behind its last operation and
+// queues { fence, fn, priv } (cbq.h). The queue is run in order, as far as the fences have
+// completed, on entry to pl_tex_upload / pl_tex_download, pl_buf_poll / pl_tex_poll and
+// pl_gpu_flush; pl_gpu_finish and pl_hip_destroy run all of it. Always on the calling thread -- a
+// callback may call back into the library, which a callback on a runtime thread
+// (hipLaunchHostFunc) may not.
+
+// the pool of fences (backend.h: plh_fence_create). An event is given back only once it has
+// completed or was never recorded.
+static int fence_get(struct gpu_priv *g, plh_event *out)
+{
+    if (g->fence_pool_n > 0) {
+        *out = g->fence_pool[--g->fence_pool_n];
+        return 0;
+    }
+    return plh_fence_create(g->device, out);
+}
+
+static void fence_put(struct gpu_priv *g, plh_event e)
+{
+    if (!e)
+        return;
+    if (g->fence_pool_n < PLH_FENCE_POOL)
+        g->fence_pool[g->fence_pool_n++] = e;
+    else
+        plh_event_destroy(e);
+}
+
+static bool cb_fence_done(void *ctx, void *fence)
+{
+    (void) ctx;
+    return plh_event_query(fence) != 0;     // (an error will not get better by waiting)
+}
+
+static void cb_fence_wait(void *ctx, void *fence)
+{
+    (void) ctx;
+    plh_event_sync(fence);
+}
+
+static void cb_fence_release(void *ctx, void *fence)
+{
+    fence_put(ctx, fence);
+}
+
+// `fn(priv)` once everything queued on stream `s` so far has completed
+static int callback_behind(struct gpu_priv *g, plh_stream s, void (*fn)(void *priv), void *priv)
+{
+    plh_event fence;
+    int err = fence_get(g, &fence);
+    if (err)
+        return err;
+    if ((err = plh_event_record(fence, s))) {
+        fence_put(g, fence);
+        return err;
+    }
+    plh_cbq_push(&g->callbacks, fence, fn, priv);
+    return 0;
+}
+
+uint64_t plh_test_stream_syncs(pl_gpu gpu)
+{
+    return GPU_PRIV(gpu)->stream_syncs;
+}
+
+static size_t plh_page_size(void)
+{
+    const long page = sysconf(_SC_PAGESIZE);
+    return page > 0 ? (size_t) page : 4096;
+}
+
+/* ------------------------------------------------------------------------ */
 /* backend object                                                            */
 
 int pl_hip_device_count(void)
@@ -205,7 +284,8 @@ pl_hip pl_hip_create(pl_log log, const struct pl_hip_params *params)
     };
     gpu->limits = (struct pl_gpu_limits) {
         .thread_safe = false,
-        .callbacks = false,
+        .callbacks = true,          // deferred, on the calling thread ("transfer callbacks" below)
+        .align_host_ptr = plh_page_size(),
         .max_buf_size = p->info.total_mem,
         .max_ubo_size = 65536,
         .max_ssbo_size = p->info.total_mem,
@@ -222,6 +302,10 @@ pl_hip pl_hip_create(pl_log log, const struct pl_hip_params *params)
         .max_dispatch = { 1u << 31, 65535, 65535 },
         .fragment_queues = 0,   // every pass is a compute pass (dispatch.c:1236)
         .compute_queues = 1,
+    };
+    gpu->import_caps.buf = PL_HANDLE_HOST_PTR;  // (gpu is the one non-const view of p->gpu)
+    p->callbacks = (struct plh_cbq) {
+        .ctx = p, .done = cb_fence_done, .wait = cb_fence_wait, .release = cb_fence_release,
     };
     memcpy(gpu->uuid, p->info.uuid, 16);
     gpu->pci = (struct pl_gpu_pci_address) {
@@ -258,8 +342,14 @@ static void hip_destroy(pl_gpu gpu)
 {
     struct gpu_priv *p = GPU_PRIV(gpu);
     plh_gpu_sync_all(gpu);
+    plh_cbq_drain(&p->callbacks, true);
     if (p->aux)
         plh_stream_destroy(p->aux);
+    if (p->io)
+        plh_stream_destroy(p->io);
+    fence_put(p, p->io_gate);
+    for (int i = 0; i < p->fence_pool_n; i++)
+        plh_event_destroy(p->fence_pool[i]);
     for (int i = 0; i < PLH_FENCES; i++)
         plh_event_destroy(p->fence[i].ev);
     for (int i = 0; i < PLH_STAGE_SLOTS; i++) {
@@ -289,7 +379,8 @@ pl_hip pl_hip_get(pl_gpu gpu)
 
 static void hip_gpu_flush(pl_gpu gpu)
 {
-    (void) gpu; // HIP submits eagerly
+    // HIP submits eagerly: nothing to push along
+    plh_cbq_drain(&GPU_PRIV(gpu)->callbacks, false);
 }
 
 static int sync_main(struct gpu_priv *p);
@@ -300,10 +391,13 @@ static void hip_gpu_finish(pl_gpu gpu)
     int err = sync_main(p);
     if (!err && p->aux && !(err = plh_stream_sync(p->aux)))
         p->done[1] = p->seq[1];
+    if (!err && p->io && !(err = plh_stream_sync(p->io)))
+        p->io_busy = false;
     if (err) {
         pl_msg(gpu->log, PL_LOG_ERR, "pl_gpu_finish: %s", plh_strerror(err));
         p->failed = true;
     }
+    plh_cbq_drain(&p->callbacks, true);
 }
 
 /* ------------------------------------------------------------------------ */
@@ -432,6 +526,13 @@ static void order_after(pl_gpu gpu, int on, uint64_t s)
 uint64_t plh_tex_order(pl_gpu gpu, int on, pl_tex reads, pl_tex writes)
 {
     struct gpu_priv *p = GPU_PRIV(gpu);
+    // (the copy stream, below: a download queued there still reads the texture about to be written)
+    if (writes && TEX_PRIV(writes)->io_pending) {
+        struct tex_priv *t = TEX_PRIV(writes);
+        if (plh_stream_wait_event(plh_gpu_stream_n(gpu, on), t->io_ev))
+            plh_stream_sync(p->io);
+        t->io_pending = false;
+    }
     if (!p->async_measure)
         return 0;
     struct tex_priv *r = reads ? TEX_PRIV(reads) : NULL, *w = writes ? TEX_PRIV(writes) : NULL;
@@ -464,6 +565,14 @@ void plh_tex_read_so_far(pl_gpu gpu, pl_tex tex, int on)
 uint64_t plh_gpu_stamp(pl_gpu gpu, int on)
 {
     struct gpu_priv *p = GPU_PRIV(gpu);
+    // (what is stamped may write a texture that no plh_tex_order call names -- error diffusion's
+    // output: it goes behind everything the copy stream still reads)
+    if (p->io_busy) {
+        if (plh_stream_wait_event(plh_gpu_stream_n(gpu, on), p->io_tail))
+            plh_stream_sync(p->io);
+        if (!on)
+            p->io_busy = false;
+    }
     return p->async_measure ? ++p->seq[on] : 0;
 }
 
@@ -491,6 +600,7 @@ void plh_gpu_reached(pl_gpu gpu, int on, uint64_t seq)
 
 static int sync_main(struct gpu_priv *p)
 {
+    p->stream_syncs++;
     const int err = plh_stream_sync(p->stream);
     if (!err)
         p->done[0] = p->seq[0];
@@ -503,6 +613,8 @@ void plh_gpu_sync_all(pl_gpu gpu)
     sync_main(p);
     if (p->aux && !plh_stream_sync(p->aux))
         p->done[1] = p->seq[1];
+    if (p->io && !plh_stream_sync(p->io))
+        p->io_busy = false;
 }
 
 static bool hip_gpu_is_failed(pl_gpu gpu)
@@ -604,6 +716,17 @@ static void hip_tex_destroy(pl_gpu gpu, pl_tex tex)
         // the allocation may still be referenced by queued work
         plh_gpu_sync_all(gpu);
         plh_free(t->ptr);
+    } else if (t->io_pending) {
+        plh_stream_sync(GPU_PRIV(gpu)->io);
+    }
+    if (t->io_ev) {
+        if (GPU_PRIV(gpu)->io_tail == t->io_ev) {
+            if (GPU_PRIV(gpu)->io_busy)
+                plh_stream_sync(GPU_PRIV(gpu)->io);
+            GPU_PRIV(gpu)->io_busy = false;
+            GPU_PRIV(gpu)->io_tail = NULL;
+        }
+        fence_put(GPU_PRIV(gpu), t->io_ev);
     }
     free(t);
 }
@@ -714,6 +837,69 @@ static void hip_tex_blit(pl_gpu gpu, const struct pl_tex_blit_params *params)
     }
 }
 
+/* ---- the copy stream ----------------------------------------------------------------------- */
+// Everything is ordered on the main stream, so a frame's download (66 MB for a 4K rgba16 target)
+// would hold back the next frame's upload and render although they share nothing with it and
+// the link carries both directions at once. A download into an IMPORTED buffer -- the one
+// transfer whose completion the caller learns from the buffer, not from the stream -- therefore
+// runs on a stream of its own:
+//   * it starts once the main stream has got to where it was queued (io_gate: the render that
+//     wrote the texture is in front of it, and so is the aux stream's part, plh_tex_order);
+//   * the texture remembers an event behind the copy (io_ev); whatever WRITES the texture next,
+//     on either stream, waits for it (plh_tex_order, plh_gpu_stamp). Readers need nothing;
+//   * the buffer's fence and the callback's are recorded on the copy stream; a buffer that is
+//     next used on the other stream makes that stream wait for its fence (buf_order);
+//   * pl_gpu_finish, pl_tex_poll, plh_gpu_sync_all and the destroy functions cover the stream.
+// Not with a caller's own stream (pl_hip_params.stream: all work is promised to be on it) and
+// not for a timed transfer (the timer's events belong to the main stream).
+static plh_stream io_stream(struct gpu_priv *g)
+{
+    if (!g->own_stream)
+        return NULL;
+    if (!g->io && plh_stream_create(g->device, &g->io))
+        g->io = NULL;
+    if (g->io && !g->io_gate && fence_get(g, &g->io_gate))
+        g->io_gate = NULL;
+    return g->io_gate ? g->io : NULL;
+}
+
+// `buf` is about to be used on stream `s`: behind its last use, if that was on the other stream
+static int buf_order(struct gpu_priv *g, pl_buf buf, plh_stream s)
+{
+    struct buf_priv *b = BUF_PRIV(buf);
+    if (!b->imported || !b->fenced || b->on_io == (g->io && s == g->io))
+        return 0;
+    return plh_stream_wait_event(s, b->fence);
+}
+
+// Something that reads or writes `buf` has just been queued on stream `s`. An imported buffer's
+// fence moves behind it; ordinary buffers keep no fence (passes use them unrecorded).
+static int buf_used(struct gpu_priv *g, pl_buf buf, plh_stream s)
+{
+    struct buf_priv *b = BUF_PRIV(buf);
+    if (!b->imported)
+        return 0;
+    const int err = plh_event_record(b->fence, s);
+    if (!err) {
+        b->fenced = true;
+        b->on_io = g->io && s == g->io;
+    }
+    return err;
+}
+
+// returns once the last queued use of an imported buffer has completed; an event that cannot be
+// waited for fails the gpu (pl_gpu_is_failed) rather than leave the buffer busy for ever
+static void buf_wait(struct gpu_priv *g, struct buf_priv *b)
+{
+    if (!b->fenced)
+        return;
+    if (plh_event_sync(b->fence)) {
+        g->failed = true;
+        plh_gpu_sync_all(&g->gpu);
+    }
+    b->fenced = false;
+}
+
 // the staging buffer of the emulated formats' `ptr` transfers, at least `size` bytes
 static void *texel_stage(struct gpu_priv *g, size_t size)
 {
@@ -758,8 +944,20 @@ static bool hip_tex_transfer(pl_gpu gpu, const struct pl_tex_transfer_params *pa
     if (params->timer)
         plh_timer_begin(gpu, params->timer, 0);
 
-    int err;
-    if (texel) {
+    // (a download into an imported buffer: beside the main stream, see "the copy stream")
+    plh_stream s = g->stream;
+    int err = 0;
+    if (!upload && params->buf && BUF_PRIV(params->buf)->imported && !params->timer && io_stream(g)) {
+        if (!(err = plh_event_record(g->io_gate, g->stream)) &&
+            !(err = plh_stream_wait_event(g->io, g->io_gate)))
+            s = g->io;
+    } else if (params->buf) {
+        err = buf_order(g, params->buf, s);
+    }
+
+    if (err) {
+        // (reported below)
+    } else if (texel) {
         const int w = rc.x1 - rc.x0;
         uint8_t *packed;
         size_t ppitch = host_pitch;
@@ -772,27 +970,33 @@ static bool hip_tex_transfer(pl_gpu gpu, const struct pl_tex_transfer_params *pa
         if (!packed) {
             err = -2;   // hipErrorOutOfMemory
         } else if (upload) {
-            err = params->buf ? 0 : plh_copy2d_h2d(g->stream, packed, ppitch, params->ptr,
+            err = params->buf ? 0 : plh_copy2d_h2d(s, packed, ppitch, params->ptr,
                                                    host_pitch, row_bytes, rows);
             if (!err)
-                err = plh_launch_texel_convert(g->stream, texel, 0, packed, ppitch, dev, t->pitch,
+                err = plh_launch_texel_convert(s, texel, 0, packed, ppitch, dev, t->pitch,
                                                w, (int) rows);
         } else {
-            err = plh_launch_texel_convert(g->stream, texel, 1, dev, t->pitch, packed, ppitch,
+            err = plh_launch_texel_convert(s, texel, 1, dev, t->pitch, packed, ppitch,
                                            w, (int) rows);
             if (!err && !params->buf)
-                err = plh_copy2d_d2h(g->stream, params->ptr, host_pitch, packed, ppitch,
+                err = plh_copy2d_d2h(s, params->ptr, host_pitch, packed, ppitch,
                                      row_bytes, rows);
         }
         if (!err && !params->buf && !params->callback)
             err = sync_main(g);
+    } else if (params->buf && BUF_PRIV(params->buf)->imported) {
+        // the caller's registered pages, by their host address: asynchronous DMA, nothing to wait
+        // for here (the buffer's fence below says when it is done)
+        uint8_t *hptr = BUF_PRIV(params->buf)->host + params->buf_offset;
+        err = upload ? plh_copy2d_h2d(s, dev, t->pitch, hptr, host_pitch, row_bytes, rows)
+                     : plh_copy2d_d2h(s, hptr, host_pitch, dev, t->pitch, row_bytes, rows);
     } else if (params->buf) {
         uint8_t *bptr = (uint8_t *) BUF_PRIV(params->buf)->ptr + params->buf_offset;
-        err = upload ? plh_copy2d_d2d(g->stream, dev, t->pitch, bptr, host_pitch, row_bytes, rows)
-                     : plh_copy2d_d2d(g->stream, bptr, host_pitch, dev, t->pitch, row_bytes, rows);
+        err = upload ? plh_copy2d_d2d(s, dev, t->pitch, bptr, host_pitch, row_bytes, rows)
+                     : plh_copy2d_d2d(s, bptr, host_pitch, dev, t->pitch, row_bytes, rows);
     } else {
-        err = upload ? plh_copy2d_h2d(g->stream, dev, t->pitch, params->ptr, host_pitch, row_bytes, rows)
-                     : plh_copy2d_d2h(g->stream, params->ptr, host_pitch, dev, t->pitch, row_bytes, rows);
+        err = upload ? plh_copy2d_h2d(s, dev, t->pitch, params->ptr, host_pitch, row_bytes, rows)
+                     : plh_copy2d_d2h(s, params->ptr, host_pitch, dev, t->pitch, row_bytes, rows);
         // pageable host memory: the reference's contract is that `ptr` may be
         // reused / is filled when the call returns (gpu.h, no callback given)
         if (!err && !params->callback)
@@ -802,37 +1006,60 @@ static bool hip_tex_transfer(pl_gpu gpu, const struct pl_tex_transfer_params *pa
     if (params->timer)
         plh_timer_end(gpu, params->timer, 0);
 
+    if (!err && s != g->stream) {
+        // whoever writes the texture next waits for this copy
+        struct tex_priv *tw = TEX_PRIV(tex);
+        if (!tw->io_ev)
+            err = fence_get(g, &tw->io_ev);
+        if (!err && !(err = plh_event_record(tw->io_ev, s))) {
+            tw->io_pending = true;
+            g->io_tail = tw->io_ev;
+            g->io_busy = true;
+        }
+        if (err)
+            plh_stream_sync(s);     // (no event to be had: the blunt way)
+    }
+    if (!err && params->buf)
+        err = buf_used(g, params->buf, s);
+    if (!err && params->callback)
+        err = callback_behind(g, s, params->callback, params->priv);
+    // A `ptr` transfer keeps what it always did, with or without a callback: on return `ptr` may
+    // be reused / is filled, and the callback has run (tests/test_gpu_texel_formats.py holds
+    // that) -- behind every callback queued before it. Only `buf` transfers are deferred.
+    if (!err && params->callback && !params->buf && !(err = sync_main(g)))
+        plh_cbq_drain(&g->callbacks, true);
+
     if (err) {
         pl_msg(gpu->log, PL_LOG_ERR, "pl_tex_%s: %s", upload ? "upload" : "download",
                plh_strerror(err));
         g->failed = true;
         return false;
     }
-    if (params->callback) {
-        sync_main(g);
-        params->callback(params->priv);
-    }
     return true;
 }
 
 static bool hip_tex_upload(pl_gpu gpu, const struct pl_tex_transfer_params *params)
 {
+    plh_cbq_drain(&GPU_PRIV(gpu)->callbacks, false);
     return hip_tex_transfer(gpu, params, true);
 }
 
 static bool hip_tex_download(pl_gpu gpu, const struct pl_tex_transfer_params *params)
 {
+    plh_cbq_drain(&GPU_PRIV(gpu)->callbacks, false);
     return hip_tex_transfer(gpu, params, false);
 }
 
 static bool stream_busy(pl_gpu gpu, uint64_t timeout)
 {
+    plh_cbq_drain(&GPU_PRIV(gpu)->callbacks, false);
     if (timeout) {
         pl_gpu_finish(gpu);
         return false;
     }
     const struct gpu_priv *p = GPU_PRIV(gpu);
-    return plh_stream_idle(p->stream) == 0 || (p->aux && plh_stream_idle(p->aux) == 0);
+    return plh_stream_idle(p->stream) == 0 || (p->aux && plh_stream_idle(p->aux) == 0) ||
+           (p->io && plh_stream_idle(p->io) == 0);
 }
 
 static bool hip_tex_poll(pl_gpu gpu, pl_tex tex, uint64_t timeout)
@@ -852,6 +1079,30 @@ static pl_buf hip_buf_create(pl_gpu gpu, const struct pl_buf_params *params)
         return NULL;
     b->buf.params = *params;
     b->buf.params.initial_data = NULL;
+    if (params->import_handle) {
+        // PL_HANDLE_HOST_PTR, page-rounded by the front-end: registered here, once, for the life
+        // of the buffer. `data` is the caller's own pointer, with or without host_mapped.
+        const struct pl_shared_mem *shmem = &params->shared_mem;
+        void *alias = NULL;
+        int err = fence_get(g, &b->fence);
+        if (!err && (err = plh_host_register(shmem->handle.ptr, shmem->size, &alias)))
+            fence_put(g, b->fence);
+        if (err) {
+            pl_msg(gpu->log, PL_LOG_ERR, "pl_buf_create: registering %zu bytes of host memory at "
+                   "%p failed: %s", shmem->size, shmem->handle.ptr, plh_strerror(err));
+            free(b);
+            return NULL;
+        }
+        b->imported = true;
+        b->reg_base = shmem->handle.ptr;
+        b->host = (uint8_t *) shmem->handle.ptr + shmem->offset;
+        b->ptr = (uint8_t *) alias + shmem->offset;
+        b->buf.data = b->host;
+        b->buf.shared_mem = *shmem;
+        if (params->initial_data)
+            memcpy(b->host, params->initial_data, params->size);
+        return &b->buf;
+    }
     b->ptr = plh_malloc(g->device, params->size);
     if (!b->ptr) {
         pl_msg(gpu->log, PL_LOG_ERR, "pl_buf_create: out of device memory");
@@ -869,9 +1120,18 @@ static pl_buf hip_buf_create(pl_gpu gpu, const struct pl_buf_params *params)
 
 static void hip_buf_destroy(pl_gpu gpu, pl_buf buf)
 {
+    struct buf_priv *b = BUF_PRIV(buf);
+    if (b->imported) {
+        // its own last use only; the memory is the caller's and stays
+        buf_wait(GPU_PRIV(gpu), b);
+        plh_host_unregister(b->reg_base);
+        fence_put(GPU_PRIV(gpu), b->fence);
+        free(b);
+        return;
+    }
     plh_gpu_sync_all(gpu);
-    plh_free(BUF_PRIV(buf)->ptr);
-    free(BUF_PRIV(buf));
+    plh_free(b->ptr);
+    free(b);
 }
 
 void *pl_hip_buf_ptr(pl_buf buf)
@@ -883,6 +1143,12 @@ void *pl_hip_buf_ptr(pl_buf buf)
 void plh_buf_write(pl_gpu gpu, pl_buf buf, size_t buf_offset, const void *data, size_t size)
 {
     struct gpu_priv *g = GPU_PRIV(gpu);
+    if (BUF_PRIV(buf)->imported) {
+        // host memory: once nothing queued reads or writes it any more, a plain copy
+        buf_wait(g, BUF_PRIV(buf));
+        memcpy(BUF_PRIV(buf)->host + buf_offset, data, size);
+        return;
+    }
     uint8_t *dst = (uint8_t *) BUF_PRIV(buf)->ptr + buf_offset;
     if (size <= PLH_STAGE_BYTES) {
         // through a pinned slot: `data` is the caller's again as soon as it is copied there,
@@ -971,6 +1237,13 @@ void plh_gpu_release_scratch(pl_gpu gpu, const void *slot)
 bool plh_buf_read(pl_gpu gpu, pl_buf buf, size_t buf_offset, void *dest, size_t size)
 {
     struct gpu_priv *g = GPU_PRIV(gpu);
+    if (BUF_PRIV(buf)->imported) {
+        buf_wait(g, BUF_PRIV(buf));
+        if (g->failed)
+            return false;
+        memcpy(dest, BUF_PRIV(buf)->host + buf_offset, size);
+        return true;
+    }
     queued_unnumbered(g);
     int err = plh_copy2d_d2h(g->stream, dest, size, (uint8_t *) BUF_PRIV(buf)->ptr + buf_offset,
                              size, size, 1);
@@ -978,20 +1251,28 @@ bool plh_buf_read(pl_gpu gpu, pl_buf buf, size_t buf_offset, void *dest, size_t 
     return !err;
 }
 
+// (an imported buffer takes part through its device alias, which is what `ptr` is)
 static void hip_buf_copy(pl_gpu gpu, pl_buf dst, size_t dst_offset, pl_buf src, size_t src_offset,
                          size_t size)
 {
-    queued_unnumbered(GPU_PRIV(gpu));
-    plh_copy2d_d2d(GPU_PRIV(gpu)->stream, (uint8_t *) BUF_PRIV(dst)->ptr + dst_offset, size,
+    struct gpu_priv *g = GPU_PRIV(gpu);
+    queued_unnumbered(g);
+    buf_order(g, dst, g->stream);
+    buf_order(g, src, g->stream);
+    plh_copy2d_d2d(g->stream, (uint8_t *) BUF_PRIV(dst)->ptr + dst_offset, size,
                    (uint8_t *) BUF_PRIV(src)->ptr + src_offset, size, size, 1);
+    buf_used(g, dst, g->stream);
+    buf_used(g, src, g->stream);
 }
 
 static bool hip_buf_copy_swap(pl_gpu gpu, pl_buf dst, size_t dst_offset, pl_buf src, size_t src_offset,
                               size_t size, int wordsize)
 {
-    queued_unnumbered(GPU_PRIV(gpu));
-    return !plh_launch_swap_words(GPU_PRIV(gpu)->stream, (const uint8_t *) BUF_PRIV(src)->ptr + src_offset,
-                                  (uint8_t *) BUF_PRIV(dst)->ptr + dst_offset, size / 4, wordsize);
+    struct gpu_priv *g = GPU_PRIV(gpu);
+    queued_unnumbered(g);
+    const int err = plh_launch_swap_words(g->stream, (const uint8_t *) BUF_PRIV(src)->ptr + src_offset,
+                                          (uint8_t *) BUF_PRIV(dst)->ptr + dst_offset, size / 4, wordsize);
+    return !err;
 }
 
 static bool hip_buf_export(pl_gpu gpu, pl_buf buf)
@@ -1001,10 +1282,38 @@ static bool hip_buf_export(pl_gpu gpu, pl_buf buf)
     return false;
 }
 
+// An ordinary buffer is busy while the streams are (passes use it without fences). An imported
+// one is busy until its own fence has completed, whatever else is queued behind it: timeout 0
+// asks, UINT64_MAX waits on the event, anything between asks and yields until the deadline.
 static bool hip_buf_poll(pl_gpu gpu, pl_buf buf, uint64_t timeout)
 {
-    (void) buf;
-    return stream_busy(gpu, timeout);
+    struct buf_priv *b = BUF_PRIV(buf);
+    if (!b->imported)
+        return stream_busy(gpu, timeout);
+
+    plh_cbq_drain(&GPU_PRIV(gpu)->callbacks, false);
+    if (!b->fenced)
+        return false;
+    if (timeout == UINT64_MAX) {
+        buf_wait(GPU_PRIV(gpu), b);
+        return false;
+    }
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    const uint64_t start = (uint64_t) ts.tv_sec * 1000000000ull + (uint64_t) ts.tv_nsec;
+    for (;;) {
+        if (plh_event_query(b->fence) != 0) {   // (done, or an error that waiting will not mend)
+            b->fenced = false;
+            return false;
+        }
+        if (!timeout)
+            return true;
+        clock_gettime(CLOCK_MONOTONIC, &ts);
+        const uint64_t now = (uint64_t) ts.tv_sec * 1000000000ull + (uint64_t) ts.tv_nsec;
+        if (now - start >= timeout)
+            return true;
+        sched_yield();
+    }
 }
 
 /* ------------------------------------------------------------------------ */

@@ -10,6 +10,7 @@
 #include <libplacebo/hip.h>
 
 #include "host_common.h"
+#include "cbq.h"
 #include "../hip/backend.h"
 
 struct fmt_priv {
@@ -65,6 +66,7 @@ struct plh_gpu_fns {
 #define PLH_STAGE_BYTES (64 * 1024)
 
 #define PLH_FENCES 16
+#define PLH_FENCE_POOL 32
 
 struct gpu_priv {
     struct pl_gpu_t gpu;
@@ -109,6 +111,21 @@ struct gpu_priv {
     // the host copy and the conversion kernel. Grow-only; freed with the gpu.
     void *texel_stage;
     size_t texel_stage_size;
+    // fences not in use (plh_fence_create): taken by imported buffers, queued callbacks and the
+    // copy stream, given back once complete, destroyed with the gpu
+    plh_event fence_pool[PLH_FENCE_POOL];
+    int fence_pool_n;
+    // deferred transfer callbacks (cbq.h), run from the calling thread
+    struct plh_cbq callbacks;
+    // whole-stream drains so far (sync_main, plh_gpu_sync_all): plh_test_stream_syncs
+    uint64_t stream_syncs;
+    // The copy stream (gpu_hip.c "the copy stream"): downloads into imported buffers run here,
+    // beside whatever the main stream does next. Created on first use, own streams only.
+    // io_gate: recorded on the main stream in front of each such download, waited for by `io`;
+    // io_tail: the event behind the latest one (a texture's io_ev); io_busy: not yet known done.
+    plh_stream io;
+    plh_event io_gate, io_tail;
+    bool io_busy;
 };
 
 #define PLH_SCRATCH_SLOTS 32
@@ -132,11 +149,24 @@ struct tex_priv {
     // the renderer's measured intermediate (written on the measuring stream, read on the main one,
     // rewritten a few frames on): the launch that reads it carries a fence (plh_gpu_fence_for_launch)
     bool fence_reads;
+    // a download queued on the copy stream still reads the texture: whoever writes it next waits
+    // for io_ev first (plh_tex_order)
+    plh_event io_ev;
+    bool io_pending;
 };
 
 struct buf_priv {
     struct pl_buf_t buf;
-    void *ptr;
+    void *ptr;          // device address of byte 0 (an imported buffer: inside the device alias)
+    // A buffer imported from a host pointer (PL_HANDLE_HOST_PTR): the caller's pages, registered
+    // for the life of the buffer. Only transfers and buffer copies ever touch it, so one fence --
+    // the last use queued so far -- says all there is to know about it.
+    bool imported;
+    void *reg_base;     // what was registered (whole pages)
+    uint8_t *host;      // host address of byte 0
+    plh_event fence;
+    bool fenced;        // `fence` has been recorded and not yet been seen complete
+    bool on_io;         // ... on the copy stream (else on the main stream)
 };
 
 #define PLH_TIMER_RING 16
@@ -204,6 +234,11 @@ void plh_gpu_order_after(pl_gpu gpu, int on, uint64_t other_seq);
 // the host has seen the result of launch `seq` of stream `on`
 void plh_gpu_reached(pl_gpu gpu, int on, uint64_t seq);
 void plh_gpu_sync_all(pl_gpu gpu);
+// Test hook: plh_host_ptr_round (host_ptr.h), the page rounding of host-pointer imports
+PL_API bool plh_test_host_ptr_round(const void *ptr, size_t offset, size_t size, size_t align,
+                                    void **out_base, size_t *out_offset, size_t *out_size);
+// Test hook: whole-stream drains performed by this pl_gpu so far
+PL_API uint64_t plh_test_stream_syncs(pl_gpu gpu);
 static inline int plh_gpu_device(pl_gpu gpu) { return GPU_PRIV(gpu)->device; }
 
 #endif // PLH_GPU_PRIV_H_
