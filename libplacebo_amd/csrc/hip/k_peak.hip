@@ -102,17 +102,33 @@ DEV peak_pq_consts peak_load_pq(const plh_op &op)
     return { f[2], f[3], f[4], f[5], f[6], f[7], f[0], f[1], op.i1 };
 }
 
+// max(x, 0) of a value that is known not to be a signalling NaN, as the one instruction it is.
+// fmaxf(x, 0) is IEEE maxNum: where the compiler cannot prove that of x (behind a select, an empty
+// asm, a block boundary) it quiets x first, `v_max_f32 x, x`, and only then takes the maximum. The
+// instruction is spelled here so that no such copy is made. (A quiet NaN gives 0 either way.)
+DEV float peak_max0(float x)
+{
+    float r;
+    asm("v_max_f32 %0, 0, %1" : "=v"(r) : "v"(x));
+    return r;
+}
+
+// FLAGS: the TRC flags of the launch where a kernel is instantiated for them (k_peak_tiles: no
+// flag is tested per pixel, and the channels -- finite products or exact plh_h2f results -- are
+// clamped by peak_max0); -1: the flags are k.flags, tested here
+template <int FLAGS = -1>
 DEV void peak_linearize_pq(float4_t &c, const peak_pq_consts &k)
 {
+    const int flags = FLAGS < 0 ? k.flags : FLAGS;
     float v[3] = { c.x, c.y, c.z };
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-        if (k.flags & PLH_TRC_CLAMP0)
-            v[i] = fmaxf(v[i], 0.0f);
+        if (flags & PLH_TRC_CLAMP0)
+            v[i] = FLAGS < 0 ? fmaxf(v[i], 0.0f) : peak_max0(v[i]);
         const float p = plh_powf(v[i], k.inv_m2);
         const float r = div1(fmaxf(p - k.c1, 0.0f), __builtin_fmaf(-k.c3, p, k.c2));
         v[i] = plh_powf(r, k.inv_m1) * k.gain;
-        if (k.flags & PLH_TRC_RESCALE)
+        if (flags & PLH_TRC_RESCALE)
             v[i] = k.out_scale * v[i] + k.out_add;
     }
     c.x = v[0]; c.y = v[1]; c.z = v[2];
@@ -138,20 +154,29 @@ DEV peak_consts peak_load_consts(const plh_op &op)
     return { { e[0], e[1], e[2] }, e[3], e[4], e[5], e[6], e[7], e[8], e[9] };
 }
 
-// luma of a linear colour -> 14 bits of PQ
-DEV uint32_t peak_luma_pq14(const float4_t &c, const peak_consts &e)
+// luma of a linear colour -> PQ
+DEV float peak_luma_pq(const float4_t &c, const peak_consts &e)
 {
     float luma = e.luma[0] * c.x + e.luma[1] * c.y + e.luma[2] * c.z;
     luma *= e.white;
     luma = plh_powf(plh_clamp(luma, 0.0f, 1.0f), e.m1);
     luma = div1(e.c1 + e.c2 * luma, 1.0f + e.c3 * luma);
-    luma = plh_powf(luma, e.m2);
-    const float cutoff = e.cutoff;
-    if (cutoff != 0.0f) {
-        // luma *= smoothstep(0, cutoff, luma)
-        const float t = plh_clamp(div1(luma, cutoff), 0.0f, 1.0f);
-        luma *= t * t * (3.0f - 2.0f * t);
-    }
+    return plh_powf(luma, e.m2);
+}
+
+// luma *= smoothstep(0, cutoff, luma)
+DEV float peak_cutoff(float luma, float cutoff)
+{
+    const float t = plh_clamp(div1(luma, cutoff), 0.0f, 1.0f);
+    return luma * (t * t * (3.0f - 2.0f * t));
+}
+
+// luma of a linear colour -> 14 bits of PQ
+DEV uint32_t peak_luma_pq14(const float4_t &c, const peak_consts &e)
+{
+    float luma = peak_luma_pq(c, e);
+    if (e.cutoff != 0.0f)
+        luma = peak_cutoff(luma, e.cutoff);
     return (uint32_t) (16383.0f * luma);
 }
 
@@ -489,6 +514,13 @@ DEV uint32_t *peak_pad_word(uint32_t *scratch, uint32_t i)
 // intermediate. Every uniform of the walk is read ONCE in front of it and pinned in SGPRs: inside
 // the loop a kernel-argument field is re-loaded at each use, every load behind a full scalar wait
 // (the first version of this kernel: 174 of them per tile, 108 us for 1080p instead of 13).
+// What is uniform over the launch is also DECIDED outside the per-pixel code (a test of a uniform
+// inside it is compiled into a compare and a select per pixel and channel):
+//   - PQ means the TRC flags every PQ source has, PLH_TRC_CLAMP0 alone: the clamp is one
+//     instruction, no rescale is computed (plh_launch_peak sends other flags to k_peak_fast);
+//   - the PLANE_MAP has 4 components or 3 (any other count: k_peak_fast). With 3 alpha is not
+//     decoded: the f16 code of its neutral value is converted once, in front of the walk;
+//   - cutoff and histogram are one uniform branch per row of two pixels each.
 template <bool F16SRC, int STORE, bool PQ>
 __global__ __launch_bounds__(64 * PEAK_WAVES)
 void k_peak_tiles(const plh_pass p_)
@@ -537,18 +569,17 @@ void k_peak_tiles(const plh_pass p_)
     const float rtx = 1.0f / (float) tiles_x;     // (uniform, in a vector register)
     uintptr_t sp = (uintptr_t) s.src.ptr, dp = (uintptr_t) p.dst.ptr;
     int spitch = s.src.pitch, dpitch = p.dst.pitch;
-    int map_n = 4;
-    float nt1 = 0.0f, nt2 = 0.0f, nt3 = 1.0f;
-    if (has_map) {
-        map_n = o_map.i1;
-        nt1 = o_map.f[1]; nt2 = o_map.f[2]; nt3 = o_map.f[3];
-    }
+    // identity PLANE_MAP of the first 3 components: alpha takes its neutral value, as an f16 code
+    // (4 components, or no PLANE_MAP: alpha is the texel's)
+    int map_n = has_map ? o_map.i1 : 4;
+    // (the conversion's result lives in a vector register: pinned there, converted once)
+    uint32_t alpha_h = plh_f2h(has_map ? o_map.f[3] : 1.0f);
+    asm volatile("" : "+v"(alpha_h));
     asm volatile("" : "+s"(w), "+s"(h), "+s"(use_hist), "+s"(sp), "+s"(dp), "+s"(spitch),
-                      "+s"(dpitch), "+s"(map_n), "+s"(nt1), "+s"(nt2), "+s"(nt3));
+                      "+s"(dpitch), "+s"(map_n));
     asm volatile("" : "+s"(pc.luma[0]), "+s"(pc.luma[1]), "+s"(pc.luma[2]), "+s"(pc.white), "+s"(pc.m1),
                       "+s"(pc.c1), "+s"(pc.c2), "+s"(pc.c3), "+s"(pc.m2), "+s"(pc.cutoff));
-    asm volatile("" : "+s"(pq.inv_m2), "+s"(pq.c1), "+s"(pq.c2), "+s"(pq.c3), "+s"(pq.inv_m1), "+s"(pq.gain),
-                      "+s"(pq.out_scale), "+s"(pq.out_add), "+s"(pq.flags));
+    asm volatile("" : "+s"(pq.inv_m2), "+s"(pq.c1), "+s"(pq.c2), "+s"(pq.c3), "+s"(pq.inv_m1), "+s"(pq.gain));
     typedef __attribute__((address_space(1))) const plh_u32x4 g_u32x4;
     typedef __attribute__((address_space(1))) plh_u32x4 g_u32x4_w;
     typedef __attribute__((address_space(1))) plh_u32x2 g_u32x2_w;
@@ -576,30 +607,49 @@ void k_peak_tiles(const plh_pass p_)
         int x0, y0;
         origin(j, x0, y0);
         const int px = min(x0, w - 2);
+        // (an odd width's last lane: the mask is empty for every tile but those of the last column,
+        // and the rows of the others branch around the two selects)
+        const bool last_px = x0 + 1 >= w;
+        const uint64_t any_last_px = __ballot(last_px);
         uint32_t lane_sum = 0, nblack = 0;
         auto fetch = [&](int k) {
             return *(g_u32x4 *) (sp + (size_t) min(y0 + 8 * k, h - 1) * (size_t) spitch + (size_t) px * 8);
         };
+        // The decoded value is pinned in its register before anything converts it to f16: the
+        // intermediate holds f16(fp32 quotient), two roundings. Left alone the compiler fuses
+        // plh_un16's last fma with the conversion (v_fma_mixlo_f16, one rounding), and codes 65455
+        // and 65519 land on the neighbouring half (k_polar_mx.hiph: mx_un16_for_f16).
+        auto decode = [](uint32_t code) {
+            float x = F16SRC ? plh_h2f((uint16_t) code) : plh_un16_3(code);
+            if (!F16SRC && STORE == 1)
+                asm volatile("" : "+v"(x));
+            return x;
+        };
         auto row = [&](int k, plh_u32x4 v) {
             const int y = y0 + 8 * k;
-            if (x0 + 1 >= w) {      // both texels are the row's last one
-                v.x = v.z; v.y = v.w;
+            uint32_t q[4] = { v.x, v.y, v.z, v.w };
+            if (any_last_px) {
+                // both texels are the row's last one (the empty asm keeps this a block of its own:
+                // two selects are cheap enough to be hoisted in front of the branch otherwise)
+                q[0] = last_px ? q[2] : q[0];
+                q[1] = last_px ? q[3] : q[1];
+                asm volatile("" : "+v"(q[0]), "+v"(q[1]));
             }
-            const uint32_t q[4] = { v.x, v.y, v.z, v.w };
             float4_t c[2];
+            uint32_t ah[2] = { alpha_h, alpha_h };      // alpha as an f16 code (STORE 1)
 #pragma unroll
             for (int i = 0; i < 2; i++) {
                 const uint32_t lo = q[2 * i], hi = q[2 * i + 1];
-                float4_t t;
-                if (F16SRC)
-                    t = { plh_h2f(lo & 0xffff), plh_h2f(lo >> 16), plh_h2f(hi & 0xffff), plh_h2f(hi >> 16) };
-                else
-                    t = { plh_un16(lo & 0xffff), plh_un16(lo >> 16), plh_un16(hi & 0xffff), plh_un16(hi >> 16) };
-                // identity PLANE_MAP of the first i1 components: the others take their neutral values
-                if (map_n < 4) t.w = nt3;
-                if (map_n < 3) t.z = nt2;
-                if (map_n < 2) t.y = nt1;
-                c[i] = t;
+                c[i] = { decode(lo & 0xffff), decode(lo >> 16), decode(hi & 0xffff), 1.0f };
+                if constexpr (STORE == 2)
+                    c[i].w = decode(hi >> 16);
+            }
+            if constexpr (STORE == 1) {
+                if (map_n >= 4) {
+#pragma unroll
+                    for (int i = 0; i < 2; i++)
+                        ah[i] = plh_f2h(decode(q[2 * i + 1] >> 16));
+                }
             }
             if constexpr (STORE == 2) {
                 // the feature plane: I of IPT of every pixel (op_features itself: bit-identical to the
@@ -630,7 +680,7 @@ void k_peak_tiles(const plh_pass p_)
 #pragma unroll
                 for (int i = 0; i < 2; i++) {
                     o[2 * i] = (uint32_t) plh_f2h(c[i].x) | ((uint32_t) plh_f2h(c[i].y) << 16);
-                    o[2 * i + 1] = (uint32_t) plh_f2h(c[i].z) | ((uint32_t) plh_f2h(c[i].w) << 16);
+                    o[2 * i + 1] = (uint32_t) plh_f2h(c[i].z) | (ah[i] << 16);
                 }
                 const uintptr_t d = dp + (size_t) y * (size_t) dpitch + (size_t) x0 * 8;
                 if (y < h && x0 + 1 < w)
@@ -638,14 +688,34 @@ void k_peak_tiles(const plh_pass p_)
                 else if (y < h && x0 < w)
                     *(g_u32x2_w *) d = (plh_u32x2) { o[0], o[1] };
             }
-            // the measurement (colorspace.c:1279-1348)
+            // the measurement (colorspace.c:1279-1348): peak_luma_pq14 of both pixels, its test of
+            // the cutoff taken once for the two
+            float luma[2];
 #pragma unroll
             for (int i = 0; i < 2; i++) {
                 if (PQ)
-                    peak_linearize_pq(c[i], pq);
-                const uint32_t y_pq = peak_luma_pq14(c[i], pc);
-                if (use_hist) {
-                    int bin = (int) y_pq >> (PQ_BITS - HIST_BITS);
+                    peak_linearize_pq<PLH_TRC_CLAMP0>(c[i], pq);
+                luma[i] = peak_luma_pq(c[i], pc);
+                // (one pixel after the other, as when a branch stood between them: interleaved, the
+                // two chains need 35 registers where the kernel is held to 32)
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            uint32_t y_pq[2];
+            if (pc.cutoff != 0.0f) {
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    y_pq[i] = (uint32_t) (16383.0f * peak_cutoff(luma[i], pc.cutoff));
+                    nblack += (uint32_t) __popcll(__ballot(y_pq[i] == 0u));
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 2; i++)
+                    y_pq[i] = (uint32_t) (16383.0f * luma[i]);
+            }
+            if (use_hist) {
+#pragma unroll
+                for (int i = 0; i < 2; i++) {
+                    int bin = (int) y_pq[i] >> (PQ_BITS - HIST_BITS);
                     bin -= HIST_BIAS;
                     bin = min(max(bin, 0), PEAK_HIST_BINS - 1);
                     const int first = __builtin_amdgcn_readfirstlane(bin);
@@ -656,11 +726,9 @@ void k_peak_tiles(const plh_pass p_)
                         atomicAdd(&blk[4 + bin], 1u);
                     }
                 }
-                lane_sum += y_pq;
-                lane_max = max(lane_max, y_pq);
-                if (pc.cutoff != 0.0f)
-                    nblack += (uint32_t) __popcll(__ballot(y_pq == 0u));
             }
+            lane_sum += y_pq[0] + y_pq[1];
+            lane_max = max(lane_max, max(y_pq[0], y_pq[1]));
         };
         if constexpr (STORE == 2) {
             // (the variant that also writes the feature plane runs alone on the main stream: both
@@ -856,8 +924,13 @@ int plh_launch_peak(hipStream_t stream, const plh_pass *pass)
     const bool feat_target = pass->dst.ptr && pass->dst.fmt == PLH_FMT_R16F;
     // (the feature plane: PEAK_DETECT FEATURES of a linear image, or PEAK_DETECT LINEARIZE FEATURES of PQ)
     const bool feat_ok = !feat_target || pass->num_ops == 2 || pass->ops[1].i0 == TRC_PQ;
+    // what k_peak_tiles is instantiated for: a PQ source's flags (the clamp, no rescale), a
+    // PLANE_MAP of 3 or 4 components (what the renderer's planes have; anything else has k_peak_fast)
+    const bool pq_plain = trc != TRC_PQ || pass->ops[pk_op].i1 == PLH_TRC_CLAMP0;
+    const bool map_ok = pass->ops[0].kind != PLH_OP_PLANE_MAP || pass->ops[0].i1 >= 3;
     if (peak_fast_applies(pass) && plh_switch(PLH_SW_PEAK_TILES) && feat_ok && pass->width >= 2 &&
-        (trc == TRC_PQ || trc == TRC_LINEAR)) {
+        (trc == TRC_PQ || trc == TRC_LINEAR) && pq_plain && map_ok) {
+        plh_trace_kernel("k_peak_tiles");
         // k_peak_tiles folds its own result (no k_peak_fold behind it)
         const bool f16 = pass->s.src.fmt == PLH_FMT_RGBA16F, store = pass->dst.ptr != NULL, pq = trc == TRC_PQ;
         const int per_slice = (tiles + PEAK_SLICES - 1) / PEAK_SLICES;
@@ -879,6 +952,7 @@ int plh_launch_peak(hipStream_t stream, const plh_pass *pass)
         return terr == hipSuccess ? 0 : -(int) terr;
     }
     if (peak_fast_applies(pass)) {
+        plh_trace_kernel("k_peak_fast");
         const bool f16 = pass->s.src.fmt == PLH_FMT_RGBA16F, store = pass->dst.ptr != NULL;
         const bool feat = store && pass->dst.fmt == PLH_FMT_R16F;
         if (f16 && feat)        hipLaunchKernelGGL((k_peak_fast<true, 2>), grid, block, 0, stream, *pass);
@@ -887,10 +961,13 @@ int plh_launch_peak(hipStream_t stream, const plh_pass *pass)
         else if (f16)           hipLaunchKernelGGL((k_peak_fast<true, 0>), grid, block, 0, stream, *pass);
         else if (store)         hipLaunchKernelGGL((k_peak_fast<false, 1>), grid, block, 0, stream, *pass);
         else                    hipLaunchKernelGGL((k_peak_fast<false, 0>), grid, block, 0, stream, *pass);
-    } else if (plh_ops_lite(pass, 0, pk_op) && plh_ops_lite(pass, PL_MIN_INT(pk_op + 1, pass->num_ops), pass->num_ops))
+    } else if (plh_ops_lite(pass, 0, pk_op) && plh_ops_lite(pass, PL_MIN_INT(pk_op + 1, pass->num_ops), pass->num_ops)) {
+        plh_trace_kernel("k_pass_peak");
         hipLaunchKernelGGL(k_pass_peak<true>, grid, block, 0, stream, *pass);
-    else
+    } else {
+        plh_trace_kernel("k_pass_peak");
         hipLaunchKernelGGL(k_pass_peak<false>, grid, block, 0, stream, *pass);
+    }
     static_assert(PLH_PEAK_COPIES % FOLD_GROUPS == 0, "copy groups");
     PLH_LAUNCH_LAST(k_peak_fold, dim3((PLH_PEAK_WORDS + FOLD_WORDS - 1) / FOLD_WORDS),
                        dim3(FOLD_WORDS * FOLD_GROUPS), 0, stream, (uint32_t *) pass->peak_buf,
