@@ -841,6 +841,10 @@ def declare(lib):
         fn("plh_test_stream_syncs", C.c_uint64, P(Gpu))
         fn("plh_test_host_ptr_round", C.c_bool, vp, C.c_size_t, C.c_size_t, C.c_size_t, P(vp),
            P(C.c_size_t), P(C.c_size_t))
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "plh_test_ortho_one_reflection"):
+        # (n_axis, n_across, row_size, pos[4][2], dir): may k_ortho_fast's one reflection serve a
+        # mirrored pass (shader_sampling.c)
+        fn("plh_test_ortho_one_reflection", C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float), C.c_int)
     return lib
 
 

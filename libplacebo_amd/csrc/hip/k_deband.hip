@@ -593,6 +593,7 @@ int plh_launch_deband(hipStream_t stream, const plh_pass *pass)
     if (deband_fast_applies(pass)) {
         const plh_sampler_args &s = pass->s;
         if (plh_switch(PLH_SW_DEBAND_LDS) && s.db_lds && s.iterations >= 1 && s.db_radius * (float) s.iterations <= 16.0f) {
+            plh_trace_kernel("k_deband_lds");
             int cus = 256;
             (void) plh_stream_device((plh_stream) stream, &cus);
             const int tiles_x = (pass->width + DBL_TW - 1) / DBL_TW;
@@ -619,6 +620,7 @@ int plh_launch_deband(hipStream_t stream, const plh_pass *pass)
         const int nbx = (pass->width + 2 * DBF_BW - 1) / (2 * DBF_BW);
         const int nby = (pass->height + DBF_BH - 1) / DBF_BH;
         const dim3 grid(nbx, nby);
+        plh_trace_kernel("k_deband_fast");
         PLH_LAUNCH_LAST(k_deband_fast, grid, dim3(DBF_BW, DBF_BH), 0, stream, *pass);
         const hipError_t err = hipGetLastError();
         return err == hipSuccess ? 0 : -(int) err;
@@ -626,6 +628,7 @@ int plh_launch_deband(hipStream_t stream, const plh_pass *pass)
     const dim3 block(DEBAND_BW, DEBAND_BH);
     const dim3 grid((pass->width + DEBAND_BW - 1) / DEBAND_BW,
                     (pass->height + DEBAND_BH - 1) / DEBAND_BH);
+    plh_trace_kernel("k_deband");
     if (plh_ops_lite(pass, 0, pass->num_ops))
         PLH_LAUNCH_LAST(k_deband<true>, grid, block, 0, stream, *pass);
     else

@@ -232,12 +232,15 @@ DEV float4_t of_decode(const uint2 v)
 DEV int of_clamp(int i, int n) { return min(max(i, 0), n - 1); }
 
 // tap address along the filtered axis: clamp, or GL_MIRRORED_REPEAT for taps that overshoot by
-// less than n (one reflection; the launcher checks n against the tap count)
+// less than n (one reflection; the launcher checks the rect and the tap count against n:
+// plh_ortho_one_reflection). The reflection is clamped as well: the lanes of a workgroup that hang
+// over the right / bottom edge of the output extrapolate `pos` by up to a workgroup's width, which
+// no rule about the rect bounds; they store nothing, but they do load.
 DEV int of_tap(int i, int n, bool mirror)
 {
     if (!mirror)
         return of_clamp(i, n);
-    return i < 0 ? -1 - i : (i >= n ? 2 * n - 1 - i : i);
+    return of_clamp(i < 0 ? -1 - i : (i >= n ? 2 * n - 1 - i : i), n);
 }
 
 // (clamp or single-reflection mirror addressing; repeat costs an integer modulo per tap ->
@@ -599,15 +602,11 @@ static int ortho_fast_variant(plh_pass *pass)
     const int enabled = plh_switch(PLH_SW_ORTHO_FAST);
     const plh_sampler_args &s = pass->s;
     const int n_axis = s.dir ? s.src.h : s.src.w;
-    bool addr_ok = s.address_mode == PLH_ADDRESS_CLAMP;
-    if (s.address_mode == PLH_ADDRESS_MIRROR && n_axis >= 2 * s.row_size) {
-        // one reflection is enough if the rect stays within one texture size of the texture
-        addr_ok = true;
-        for (int c = 0; c < 4; c++) {
-            for (int k = 0; k < 2; k++)
-                addr_ok = addr_ok && s.pos[c][k] > -0.9f && s.pos[c][k] < 1.9f;
-        }
-    }
+    const int n_across = s.dir ? s.src.w : s.src.h;
+    // mirror: where one reflection reaches every tap of the rect (of_tap)
+    const bool addr_ok = s.address_mode == PLH_ADDRESS_CLAMP ||
+                         (s.address_mode == PLH_ADDRESS_MIRROR &&
+                          plh_ortho_one_reflection(n_axis, n_across, s.row_size, s.pos, s.dir));
     if (s.use_linear) {
         // the LIN variant: run-time tap count (even, <= 16); no colour ops, or -- packed sources:
         // the last pass of a downscale in linear light, pl_render_default_params 4K -> 1080p -- the
@@ -979,8 +978,10 @@ extern "C" int plh_lowpass2_applies(const struct plh_lowpass2 *args)
         a.n_h < 2 || (a.n_v & 1) || (a.n_h & 1) || a.mid_w != a.src.w || a.mid_h != a.dst.h ||
         a.dst.w < 1 || a.dst.h < 1)
         return 0;
-    // one reflection only (of_tap), as k_ortho_fast's launcher requires
-    if (a.mirror && (a.src.w < 16 || a.src.h < 16))
+    // one reflection only (of_tap), as k_ortho_fast's launcher requires: either pass's taps, and the
+    // tile's columns and rows, which are those taps
+    if (a.mirror && (!plh_ortho_one_reflection(a.src.h, a.src.w, a.n_v, a.pos_v, 1) ||
+                     !plh_ortho_one_reflection(a.mid_w, a.mid_h, a.n_h, a.pos_h, 0)))
         return 0;
     // (a lane owns two columns of the tile: 128 at most -- ratios up to 3.5 with the widened bicubic)
     return a.rows_cap >= a.n_v && a.rows_cap <= 4 * LP2_KR && a.cols_cap >= a.n_h && a.cols_cap <= 128 && !(a.cols_cap & 3) &&
@@ -994,6 +995,7 @@ extern "C" int plh_launch_lowpass2(plh_stream stream_, const struct plh_lowpass2
         return 1;
     const plh_lowpass2 &a = *args;
     const size_t shmem = lowpass2_lds(a);
+    plh_trace_kernel("k_lowpass2");
     const dim3 grid((a.dst.w + LP2_TW - 1) / LP2_TW, (a.dst.h + LP2_TH - 1) / LP2_TH);
     if (a.linear_trick)
         PLH_LAUNCH_LAST(k_lowpass2<true>, grid, dim3(LP2_NT), shmem, stream, a);

@@ -569,6 +569,9 @@ struct plh_lowpass2 {
 // 0, a negative error, or 1 = not a shape the fused kernel takes (nothing launched)
 int plh_launch_lowpass2(plh_stream stream, const struct plh_lowpass2 *args);
 int plh_lowpass2_applies(const struct plh_lowpass2 *args);
+// may the single reflection of k_ortho_fast's / k_lowpass2's mirrored addressing serve every tap of
+// every pixel of a separable pass with these `pos` corners (host: shader_sampling.c)
+int plh_ortho_one_reflection(int n_axis, int n_across, int row_size, const float pos[4][2], int dir);
 int plh_launch_errdiff(plh_stream stream, const struct plh_errdiff_args *args);
 // up = 0: a downscale pass, 1: an upscale pass
 int plh_launch_blur(plh_stream stream, const struct plh_blur_args *args, int up);

@@ -474,6 +474,43 @@ int plh_test_polar_fusable_ops(const int *kinds, int n)
     return 1;
 }
 
+/* ---- mirrored addressing of the fast separable kernels ------------------------------------------ */
+
+// k_ortho_fast / k_lowpass2 address a mirrored tap with ONE reflection (of_tap, k_ortho.hip), which
+// is GL_MIRRORED_REPEAT only for an index in [-n, 2n). May it serve every tap of every pixel of this
+// pass? From the kernel's own expressions over the rect's corners (a pixel's position is a blend of
+// them):
+//   along the filtered axis   fl = floor(pos * n_axis - 0.5); taps fl - (N/2 - 1) .. fl + N/2, and
+//                             fl + N/2 + 1 where two pixels share a window (k_ortho_fast, `extra`)
+//   across it                 floor(pos * n_across)
+// each with one texel of margin for the float32 rounding of the per-pixel blend. The texture also
+// has to hold two windows (n_axis >= 2 N), as ever.
+int plh_ortho_one_reflection(int n_axis, int n_across, int row_size, const float pos[4][2], int dir)
+{
+    if (n_axis < 1 || n_across < 1 || row_size < 1 || n_axis < 2 * row_size)
+        return 0;
+    const int a = dir ? 1 : 0, o = 1 - a;
+    double lo_a = INFINITY, hi_a = -INFINITY, lo_o = INFINITY, hi_o = -INFINITY;
+    for (int c = 0; c < 4; c++) {
+        const double fa = floor((double) pos[c][a] * n_axis - 0.5);
+        const double fo = floor((double) pos[c][o] * n_across);
+        if (!isfinite(fa) || !isfinite(fo))
+            return 0;
+        lo_a = fmin(lo_a, fa); hi_a = fmax(hi_a, fa);
+        lo_o = fmin(lo_o, fo); hi_o = fmax(hi_o, fo);
+    }
+    const int half = row_size / 2;
+    return lo_a - (half - 1) - 1 >= -(double) n_axis && hi_a + (half + 1) + 1 <= 2.0 * n_axis - 1 &&
+           lo_o - 1 >= -(double) n_across && hi_o + 1 <= 2.0 * n_across - 1;
+}
+
+// for tests/test_ortho_mirror_guard.py
+PL_API int plh_test_ortho_one_reflection(int n_axis, int n_across, int row_size, const float *pos, int dir);
+int plh_test_ortho_one_reflection(int n_axis, int n_across, int row_size, const float *pos, int dir)
+{
+    return plh_ortho_one_reflection(n_axis, n_across, row_size, (const float (*)[2]) pos, dir);
+}
+
 bool plh_shader_sample_polar_fused(pl_shader sh, const pl_shader pre,
                                    const struct pl_sample_src *src,
                                    const struct pl_sample_filter_params *params)

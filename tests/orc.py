@@ -133,10 +133,12 @@ def _src(img, rect, address_mode):
 
 
 def sample_simple(img, kind, out_w, out_h, rect=None, scale=1.0, address_mode=0,
-                  threshold=0.0):
+                  threshold=0.0, size=None):
+    """`size`: the rect's width and height where they are not `rect`'s own (setup_src takes the
+    ratios from the rect it was given, the corners from the one it binds: util.bound_rect)"""
     s, keep = _src(img, rect, address_mode)
     out = np.empty(_out_shape(out_w, out_h), np.float32)
-    rw = abs(s.rect[2] - s.rect[0]); rh = abs(s.rect[3] - s.rect[1])
+    rw, rh = size or (abs(s.rect[2] - s.rect[0]), abs(s.rect[3] - s.rect[1]))
     lib().orc_sample_simple(C.byref(s), kind, C.c_float(scale), C.c_float(out_w / rw),
                             C.c_float(out_h / rh), C.c_float(threshold), out_w, out_h, _p(out))
     return out

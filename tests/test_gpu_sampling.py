@@ -105,7 +105,7 @@ def polar_pipeline(g, src, dw, dh, cfg_name="ewa_lanczos", comps=3, dither_depth
 
 
 def polar_oracle(src, dw, dh, f, comps=3, dither_depth=None, out_fmt="rgba16", antiring=0.0,
-                 rect=None, gather=None, matrix=None):
+                 rect=None, gather=None, matrix=None, address_mode=0):
     tex = orc.tex_decode(src, "rgba16")
     h_, w_ = tex.shape[:2]
     # PASS A: pl_shader_sample_direct -> rgba16hf FBO
@@ -113,7 +113,7 @@ def polar_oracle(src, dw, dh, f, comps=3, dither_depth=None, out_fmt="rgba16", a
     w, radius, radius_zero = orc.filter_generate_polar(f)
     gather = (not radius < 6.0) if gather is None else gather
     out = orc.sample_polar(img, w, radius, radius_zero, dw, dh, mask=(1 << comps) - 1,
-                           antiring=antiring, rect=rect, gather_order=gather)
+                           antiring=antiring, rect=rect, gather_order=gather, address_mode=address_mode)
     if dither_depth:
         orc.dither(out, matrix, dither_depth)
     return orc.tex_encode(out, out_fmt)

@@ -28,8 +28,6 @@ path in SCALERS, which also says where on each path the curve sits. At least hal
 pixels take part. What this sees is therefore what f16 resolves: a wrong curve, a missing black
 scaling (next to black an f16 ulp is 1e-6 of the range), a wrong branch of a curve whose pieces differ.
 """
-import contextlib
-import os
 
 import numpy as np
 import pytest
@@ -38,6 +36,7 @@ import libplacebo_amd as pl
 import orc
 import transfer_f64 as t64
 from test_transfer_f64 import RENDER_CURVES, luma_coeffs, nominal, oracle
+from util import env
 
 pytestmark = pytest.mark.gpu
 
@@ -50,18 +49,6 @@ def color_kw(trc):
     return dict(HDR) if trc in ("pq", "hlg") else {}
 
 
-@contextlib.contextmanager
-def env(**kw):
-    old = {k: os.environ.get(k) for k in kw}
-    os.environ.update(kw)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def render(gpu, capfd, img, sfmt, scsp, dw, dh, dfmt, dcsp, params, **e):

@@ -315,3 +315,77 @@ def test_distort_against_a_numpy_bilinear_resampling():
     want[..., 3] *= fade(u, 1 / sw) * fade(v, 1 / sh)
     assert np.abs(got - want).max() < 2e-5, float(np.abs(got - want).max())
     assert (got[..., 3] == 0).any() and (got[..., 3] > 0.99).any()
+
+
+# ---- REPEAT / MIRROR addressing: the periods written out --------------------------------------
+
+PAD_X, PAD_Y = 48, 24       # 32 x 16 -> 128 x 64
+
+
+def written_out(img, mode):
+    """The texture as REPEAT / MIRROR addressing continues it, as a larger texture: np.pad's "wrap",
+    or "symmetric" -- GL_MIRRORED_REPEAT, the edge texel doubled. Nothing of the oracle's wrap()."""
+    return np.pad(img, ((PAD_Y, PAD_Y), (PAD_X, PAD_X), (0, 0)), mode={1: "wrap", 2: "symmetric"}[mode])
+
+
+def shifted(rect):
+    return (rect[0] + PAD_X, rect[1] + PAD_Y, rect[2] + PAD_X, rect[3] + PAD_Y)
+
+
+PAD_RECTS = [(-8, -4, 40, 20), (-24.5, -12.25, 56.5, 28.25), (40, -4, -8, 20)]
+
+
+@pytest.mark.parametrize("rect", PAD_RECTS)
+@pytest.mark.parametrize("mode", [1, 2])
+def test_repeat_and_mirror_equal_clamped_sampling_of_the_periods_written_out(rect, mode):
+    """The oracle and the kernels share the wrap() formula by authorship; this does not. Sampling a
+    texture under REPEAT or MIRROR is sampling, under CLAMP, the larger texture in which the periods
+    stand written out, the rect moved by the padding. With power-of-two sizes (32 x 16 in 128 x 64,
+    64 x 32 outputs, rects on quarter texels) every position is exact in float32 in either form, so
+    the two frames are the same bit for bit: nearest, bilinear, the separable sampler (three
+    filters, both directions) and the polar one. (The four-tap family adds pt-scaled offsets to
+    positions of different magnitude in the two forms and agrees to a few 1e-6 only; debanding rounds
+    its tap positions. Both read through the same texel().)"""
+    img = orc.tex_decode(util.random_rgba16(32, 16, seed=21), "rgba16")
+    big = written_out(img, mode)
+    assert big.shape == (64, 128, 4)
+    # (the padding is what it should be, stated without modulo arithmetic)
+    if mode == 1:
+        assert np.array_equal(big[PAD_Y - 16:PAD_Y, PAD_X - 32:PAD_X], img)
+    else:
+        assert np.array_equal(big[PAD_Y - 16:PAD_Y, PAD_X - 32:PAD_X], img[::-1, ::-1])
+        assert np.array_equal(big[PAD_Y + 16:PAD_Y + 32, PAD_X:PAD_X + 32], img[::-1])
+
+    for kind in (orc.S_NEAREST, orc.S_BILINEAR):
+        a = orc.sample_simple(img, kind, 64, 32, rect=rect, address_mode=mode)
+        b = orc.sample_simple(big, kind, 64, 32, rect=shifted(rect))
+        assert np.array_equal(a, b), (kind, float(np.abs(a - b).max()))
+        assert a.std() > 0.1
+
+    for mk in (orc.lanczos, orc.mitchell, orc.triangle):
+        for direction in (0, 1):
+            # only `direction` scales: the other axis 1 : 1 over a whole number of texels
+            if direction == 0:
+                r = (rect[0], np.ceil(rect[1]), rect[2], np.floor(rect[3]))
+                ow, oh = 64, int(abs(r[3] - r[1]))
+                ratio = ow / abs(r[2] - r[0])
+            else:
+                lo, hi = sorted((rect[0], rect[2]))
+                lo, hi = np.ceil(lo), np.floor(hi)
+                r = (lo, rect[1], hi, rect[3]) if rect[0] < rect[2] else (hi, rect[1], lo, rect[3])
+                ow, oh = int(hi - lo), 32
+                ratio = oh / abs(r[3] - r[1])
+            f = mk(blur=1.0 / ratio if ratio < 1.0 else 0.0)
+            rows, n, radius, rz = orc.filter_generate_ortho(f)
+            rows = orc.ortho_lut_rows(rows, n, radius == rz)
+            kw = dict(use_linear=radius == rz)
+            a = orc.sample_ortho(img, rows, n, direction, ow, oh, rect=r, address_mode=mode, **kw)
+            b = orc.sample_ortho(big, rows, n, direction, ow, oh, rect=shifted(r), **kw)
+            assert np.array_equal(a, b), (direction, n, float(np.abs(a - b).max()))
+
+    ratio = 64 / abs(rect[2] - rect[0])
+    w, radius, rz = orc.filter_generate_polar(orc.ewa_lanczos(blur=1.0 / ratio if ratio < 1.0 else 0.0))
+    for gather in (False, True):
+        a = orc.sample_polar(img, w, radius, rz, 64, 32, rect=rect, address_mode=mode, gather_order=gather)
+        b = orc.sample_polar(big, w, radius, rz, 64, 32, rect=shifted(rect), gather_order=gather)
+        assert np.array_equal(a, b), (gather, float(np.abs(a - b).max()))

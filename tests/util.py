@@ -1,5 +1,6 @@
 """Shared helpers for the parity tests: synthetic frames and
 the libc rand() seeding the blue-noise generator needs to be reproducible."""
+import contextlib
 import ctypes as C
 
 import os
@@ -11,6 +12,48 @@ _libc = C.CDLL("libc.so.6")
 
 def srand(seed=1):
     _libc.srand(seed)
+
+
+@contextlib.contextmanager
+def env(**kw):
+    """with util.env(PL_HIP_ORTHO_FAST="0"): the library reads its switches per launch"""
+    old = {k: os.environ.get(k) for k in kw}
+    os.environ.update(kw)
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+@contextlib.contextmanager
+def kernel_trace(capfd, **e):
+    """with util.kernel_trace(capfd) as kernels: ...  -- afterwards `kernels` lists the kernels that
+    took the launches inside the block (PL_HIP_PASS_TRACE: "[plh] kernel <name>" on stderr), in order"""
+    kernels = []
+    capfd.readouterr()
+    with env(PL_HIP_PASS_TRACE="1", **e):
+        yield kernels
+    kernels += [ln.split()[-1] for ln in capfd.readouterr().err.splitlines()
+                if ln.startswith("[plh] kernel ")]
+
+
+def bound_rect(rect):
+    """The source rect as setup_src binds it (src/shaders/sampling.c:137-142: x1 = x0 + (x1 - x0), in
+    float32): what the tex_coord corners come from. For ends that float32 does not hold exactly this
+    can be an ulp away from the rect that was passed in, and with it every tap position."""
+    f = np.float32
+    x0, y0, x1, y1 = (f(v) for v in rect)
+    return (float(x0), float(y0), float(f(x0 + f(x1 - x0))), float(f(y0 + f(y1 - y0))))
+
+
+def rect_size(rect):
+    """|width|, |height| of a source rect as setup_src measures them: in float32"""
+    f = np.float32
+    return float(abs(f(rect[2]) - f(rect[0]))), float(abs(f(rect[3]) - f(rect[1])))
 
 
 def chirp_rgba16(w, h, alpha=65535):
