@@ -347,8 +347,7 @@ extern "C" int plh_launch_clear(plh_stream s, const struct plh_view *dst, const 
     const dim3 block(64, 4), grid((dst->w + 63) / 64, (dst->h + 3) / 4);
     float4_t c = { color[0], color[1], color[2], color[3] };
     hipLaunchKernelGGL(k_clear, grid, block, 0, (hipStream_t) s, *dst, c);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }
 
 // pl_buf_copy_swap (reference src/gpu/utils.c:1065-1138: a GLSL compute pass through the GPU's own
@@ -371,8 +370,7 @@ extern "C" int plh_launch_swap_words(plh_stream s, const void *src, void *dst, s
     const size_t groups = (words + 255) / 256;
     hipLaunchKernelGGL(k_swap_words, dim3((unsigned) groups), dim3(256), 0, (hipStream_t) s,
                        (const uint32_t *) src, (uint32_t *) dst, words, wordsize);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }
 
 // pl_frame_clear_tiles (src/renderer.c:4116-4170): the reference fills a plane through a fragment
@@ -396,8 +394,7 @@ extern "C" int plh_launch_clear_tiles(plh_stream s, const struct plh_view *dst, 
     const dim3 block(64, 4), grid((dst->w + 63) / 64, (dst->h + 3) / 4);
     const float4_t a = { c0[0], c0[1], c0[2], c0[3] }, b = { c1[0], c1[1], c1[2], c1[3] };
     hipLaunchKernelGGL(k_clear_tiles, grid, block, 0, (hipStream_t) s, *dst, a, b, kx, ky);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }
 
 /* ---- the PQ transfer pair as piecewise cubics (pqseg.hiph) ------------------------------------- */

@@ -164,6 +164,5 @@ extern "C" int plh_launch_blur(plh_stream stream, const plh_blur_args *args, int
         PLH_LAUNCH_LAST(k_blur<true>, grid, block, 0, (hipStream_t) stream, *args);
     else
         PLH_LAUNCH_LAST(k_blur<false>, grid, block, 0, (hipStream_t) stream, *args);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

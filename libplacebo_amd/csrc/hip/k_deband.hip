@@ -614,16 +614,14 @@ int plh_launch_deband(hipStream_t stream, const plh_pass *pass)
             else
                 DBL_LAUNCH(32);
 #undef DBL_LAUNCH
-            const hipError_t err = hipGetLastError();
-            return err == hipSuccess ? 0 : -(int) err;
+            return plh_launch_status();
         }
         const int nbx = (pass->width + 2 * DBF_BW - 1) / (2 * DBF_BW);
         const int nby = (pass->height + DBF_BH - 1) / DBF_BH;
         const dim3 grid(nbx, nby);
         plh_trace_kernel("k_deband_fast");
         PLH_LAUNCH_LAST(k_deband_fast, grid, dim3(DBF_BW, DBF_BH), 0, stream, *pass);
-        const hipError_t err = hipGetLastError();
-        return err == hipSuccess ? 0 : -(int) err;
+        return plh_launch_status();
     }
     const dim3 block(DEBAND_BW, DEBAND_BH);
     const dim3 grid((pass->width + DEBAND_BW - 1) / DEBAND_BW,
@@ -633,6 +631,5 @@ int plh_launch_deband(hipStream_t stream, const plh_pass *pass)
         PLH_LAUNCH_LAST(k_deband<true>, grid, block, 0, stream, *pass);
     else
         PLH_LAUNCH_LAST(k_deband<false>, grid, block, 0, stream, *pass);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

@@ -561,14 +561,12 @@ extern "C" int plh_launch_deinterlace(plh_stream stream_, const struct plh_pass 
         case 3: PLH_LAUNCH_LAST((k_deint_rows<uint8_t, true>), grid, block, 0, stream, *pass); break;
         default: PLH_LAUNCH_LAST((k_deint_rows<uint16_t, true>), grid, block, 0, stream, *pass); break;
         }
-        const hipError_t err = hipGetLastError();
-        return err == hipSuccess ? 0 : -(int) err;
+        return plh_launch_status();
     }
     const dim3 grid((pass->width + DEINT_BW - 1) / DEINT_BW, (pairs + DEINT_BH - 1) / DEINT_BH);
     if (plh_ops_lite(pass, 0, pass->num_ops))
         PLH_LAUNCH_LAST(k_deinterlace<true>, grid, block, 0, stream, *pass);
     else
         PLH_LAUNCH_LAST(k_deinterlace<false>, grid, block, 0, stream, *pass);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

@@ -107,6 +107,5 @@ extern "C" int plh_launch_errdiff(plh_stream stream, const plh_errdiff_args *arg
         (void) plh_kernel_needs_lds((const void *) k_errdiff, stream, 160 * 1024, &lds_done);
     hipLaunchKernelGGL(k_errdiff, dim3(1), dim3(args->block_size), shmem, (hipStream_t) stream,
                        *args);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

@@ -31,6 +31,5 @@ extern "C" int plh_launch_white_noise(hipStream_t stream, float *plane, int stri
 {
     hipLaunchKernelGGL(k_white_noise, dim3((w + 63) / 64, (h + 3) / 4), dim3(256), 0, stream,
                        plane, stride, w, h, x0, y0, seed);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

@@ -666,8 +666,7 @@ int plh_launch_ortho(hipStream_t stream, const plh_pass *pass)
             case PLH_FMT_R16F:    launch_ortho_fast<PLH_FMT_R16F>(stream, &local, epi); break;
             default:              launch_ortho_fast<PLH_FMT_RG16F>(stream, &local, epi); break;
             }
-            const hipError_t err = hipGetLastError();
-            return err == hipSuccess ? 0 : -(int) err;
+            return plh_launch_status();
         }
     }
     const dim3 block(ORTHO_BW, ORTHO_BH);
@@ -678,8 +677,7 @@ int plh_launch_ortho(hipStream_t stream, const plh_pass *pass)
         PLH_LAUNCH_LAST(k_ortho<true>, grid, block, 0, stream, *pass);
     else
         PLH_LAUNCH_LAST(k_ortho<false>, grid, block, 0, stream, *pass);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }
 
 
@@ -1001,6 +999,5 @@ extern "C" int plh_launch_lowpass2(plh_stream stream_, const struct plh_lowpass2
         PLH_LAUNCH_LAST(k_lowpass2<true>, grid, dim3(LP2_NT), shmem, stream, a);
     else
         PLH_LAUNCH_LAST(k_lowpass2<false>, grid, dim3(LP2_NT), shmem, stream, a);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

@@ -135,6 +135,5 @@ extern "C" int plh_launch_overlay(plh_stream stream_, const struct plh_pass *pas
         return 0;
     hipLaunchKernelGGL(k_overlay, dim3(args->num_tiles), dim3(PLH_OVERLAY_TILE * PLH_OVERLAY_TILE),
                        0, (hipStream_t) stream_, *pass, *args);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

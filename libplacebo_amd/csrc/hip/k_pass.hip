@@ -12,7 +12,6 @@
 #include <stdio.h>
 
 #include <string.h>
-#include <vector>
 #include "colorops.hiph"
 #include "backend.h"
 #include "samplers.hiph"
@@ -847,6 +846,16 @@ static bool pass_mix_applies(plh_pass *pass, plh_mixplan *m)
     return pass->epi.enabled;
 }
 
+// lut3d_tricubic: the gamut LUT op with its cubic flag set
+static bool pass_has_tricubic(const plh_pass *pass)
+{
+    for (int i = 0; i < pass->num_ops; i++) {
+        if (pass->ops[i].kind == PLH_OP_GAMUT_LUT && pass->ops[i].f[3] != 0.0f)
+            return true;
+    }
+    return false;
+}
+
 // the shape k_pass_native is written for
 static bool pass_native_applies(const plh_pass *pass, bool features = false)
 {
@@ -862,13 +871,9 @@ static bool pass_native_applies(const plh_pass *pass, bool features = false)
         return pass->dst.fmt == PLH_FMT_R16F && pass->num_ops == 1 && pass->ops[0].kind == PLH_OP_FEATURES;
     if (pass->dst.fmt != PLH_FMT_RGBA16 && pass->dst.fmt != PLH_FMT_RGBA16F)
         return false;
-    for (int i = 0; i < pass->num_ops; i++) {
-        const int k = pass->ops[i].kind;
-        if (k == PLH_OP_MIX_ADD || k == PLH_OP_MIX_END || k == PLH_OP_PEAK_DETECT ||
-            (k == PLH_OP_GAMUT_LUT && pass->ops[i].f[3] != 0.0f))
-            return false;   // (frame mixing, the measurement and the tricubic lookup have their own kernels)
-    }
-    return true;
+    // (frame mixing, the measurement and the tricubic lookup have their own kernels)
+    return !plh_pass_has_op(pass, PLH_OP_MIX_ADD) && !plh_pass_has_op(pass, PLH_OP_MIX_END) &&
+           !plh_pass_has_op(pass, PLH_OP_PEAK_DETECT) && !pass_has_tricubic(pass);
 }
 
 template <bool LITE>
@@ -932,530 +937,6 @@ static void launch_bilinear_fast(hipStream_t stream, const plh_pass *pass, int i
 #undef BF_LAUNCH
 }
 
-/*
- * k_bilinear_tab: k_bilinear_fast with the geometry taken from tables -- VERDICT r03 item 6, the
- * experiment r03 did not run: ONE 2x2 cell per lane (the shape that wins: 32 400 short waves at
- * 1080p -> 4K) and no per-pixel geometry at all.
- *
- * What k_bilinear_fast computes per pixel -- the interpolated attribute, u = pos * size - 1/2,
- * floor, fract, and the tests that the four pixels of a cell share one footprint and that the
- * weights are separable -- depends on the pixel only through its column (x) and its row (y) for
- * an axis-aligned rect, up to the rounding of the attribute interpolation. Whether it does, bit
- * for bit, is established ONCE per geometry by k_bilinear_tab_build, which evaluates every output
- * pixel with k_bilinear_fast's own arithmetic, writes the per-column / per-row tables
- * { base texel, weight } from row 0 / column 0 and counts the pixels that deviate from them; the
- * host then checks that the two pixels of every cell share their base texel. Only a geometry
- * with zero deviations (any full-frame integer upscale) gets this kernel, so its frames are
- * k_bilinear_fast's bit for bit (tests/test_gpu_kernel_variants.py). Per lane: the two column
- * entries (one 16-byte load), the two row entries (uniform per wave: scalar loads), the four
- * texels and the dither values, all in flight together; then decode, 8 blends per channel,
- * epilogue, one 16-byte store per row.
- */
-struct bl_entry { int32_t base; float w; };
-
-__global__ __launch_bounds__(256)
-void k_bilinear_tab_build(const plh_pass p_, bl_entry *cols, bl_entry *rows, uint32_t *deviating,
-                          float *colw, float *roww)
-{
-    const plh_pass &p = plh_kernarg_pass();
-    const plh_sampler_args &s = p.s;
-    const int idx = blockIdx.x * 64 + (threadIdx.x & 63), idy = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (idx >= p.width || idy >= p.height)
-        return;
-    const float sw = (float) s.src.w, sh = (float) s.src.h;
-    // (k_bilinear_fast, stage_a: the same statements in the same order)
-    auto at = [&](int x, int y, float &fu, float &ax, float &fw, float &ay) {
-        const float mx = p.out_scale[0] * ((float) x + 0.5f);
-        const float a0 = plh_mix(s.pos[0][0], s.pos[1][0], mx), a1 = plh_mix(s.pos[2][0], s.pos[3][0], mx);
-        const float b0 = plh_mix(s.pos[0][1], s.pos[1][1], mx), b1 = plh_mix(s.pos[2][1], s.pos[3][1], mx);
-        const float my = p.out_scale[1] * ((float) y + 0.5f);
-        const float px = plh_mix(a0, a1, my), py = plh_mix(b0, b1, my);
-        const float u = px * sw - 0.5f, w = py * sh - 0.5f;
-        fu = __builtin_floorf(u); fw = __builtin_floorf(w);
-        ax = u - fu; ay = w - fw;
-    };
-    float fu, ax, fw, ay, cu, cax, cw, cay, ru, rax, rw, ray;
-    at(idx, idy, fu, ax, fw, ay);
-    at(idx, 0, cu, cax, cw, cay);       // the column's entry comes from row 0 ...
-    at(0, idy, ru, rax, rw, ray);       // ... the row's from column 0
-    if (fu != cu || __float_as_uint(ax) != __float_as_uint(cax) ||
-        fw != rw || __float_as_uint(ay) != __float_as_uint(ray))
-        atomicAdd(deviating, 1u);
-    // (the weight arrays carry one extra entry at either end, repeating the first / last weight:
-    // the cell that sticks out of the rect reads them)
-    if (idy == 0) {
-        cols[idx] = { (int32_t) fu, ax };
-        colw[idx + 1] = ax;
-        if (idx == 0) colw[0] = ax;
-        if (idx == p.width - 1) colw[p.width + 1] = ax;
-    }
-    if (idx == 0) {
-        rows[idy] = { (int32_t) fw, ay };
-        roww[idy + 1] = ay;
-        if (idy == 0) roww[0] = ay;
-        if (idy == p.height - 1) roww[p.height + 1] = ay;
-    }
-}
-
-template <bool F16SRC, bool RGB>
-__global__ __launch_bounds__(BF_BW * BF_BH)
-void k_bilinear_tab(const plh_pass p_, const float *colw_, const float *roww_, int b0x, int b0y)
-{
-    const plh_pass &p = plh_kernarg_pass();
-    const plh_sampler_args &s = p.s;
-    constexpr int NCH = RGB ? 3 : 4;
-    // every uniform read once and pinned (k_bilinear_fast says why), pointers as integers
-    int W = p.width, H = p.height, padx = p.cell_padx, pady = p.cell_pady;
-    int spitch = s.src.pitch, srcw = s.src.w, srch = s.src.h;
-    int dmask = p.epi.mask, dsize = p.epi.size, has_dither = p.epi.has_dither, has_scale = p.epi.has_scale;
-    int fx0 = p.frag_x0, fy0 = p.frag_y0, bx = p.base_x, by = p.base_y, dirx = p.dir_x, diry = p.dir_y;
-    int dw = p.dst.w, dh = p.dst.h, dpitch = p.dst.pitch, nt = p.nt_store;
-    float ds = p.epi.dscale, di = p.epi.dinv, sc = p.epi.scale, alpha = p.epi.alpha, sscale = s.scale;
-    uintptr_t sp = (uintptr_t) s.src.ptr, dmat = (uintptr_t) p.epi.matrix, dptr = (uintptr_t) p.dst.ptr;
-    uintptr_t colw = (uintptr_t) colw_, roww = (uintptr_t) roww_;
-    asm volatile("" : "+s"(W), "+s"(H), "+s"(padx), "+s"(pady), "+s"(spitch), "+s"(srcw), "+s"(srch),
-                      "+s"(dmask), "+s"(dsize), "+s"(has_dither), "+s"(has_scale), "+s"(fx0), "+s"(fy0));
-    asm volatile("" : "+s"(bx), "+s"(by), "+s"(dirx), "+s"(diry), "+s"(dw), "+s"(dh), "+s"(dpitch), "+s"(nt),
-                      "+s"(ds), "+s"(di), "+s"(sc), "+s"(alpha), "+s"(sscale));
-    asm volatile("" : "+s"(sp), "+s"(dmat), "+s"(dptr), "+s"(colw), "+s"(roww), "+s"(b0x), "+s"(b0y));
-    typedef BF_GLOBAL const float gfloat;
-
-    const int cx = blockIdx.x * BF_BW + threadIdx.x;
-    // (a wave is one row of cells: its row weights are uniform)
-    const int cy = blockIdx.y * BF_BH + __builtin_amdgcn_readfirstlane(threadIdx.y);
-    const int idx0 = 2 * cx - padx, idy0 = 2 * cy - pady;
-    if (idx0 >= W || idy0 >= H)
-        return;
-
-    // Everything the cell needs from memory is asked for at once. The footprint comes from the
-    // CELL index, not from a table: the host has checked that the base texel of column X is
-    // b0x + ((X + pad) >> 1) -- b0x + cx for both pixels of cell cx -- so the texel loads do not
-    // wait for the weight loads (with the addresses taken from the tables the kernel was two
-    // dependent memory round trips long: 27 us against 19).
-    const int x0 = min(max(b0x + cx, 0), srcw - 1), x1 = min(max(b0x + cx + 1, 0), srcw - 1);
-    const int y0 = min(max(b0y + cy, 0), srch - 1), y1 = min(max(b0y + cy + 1, 0), srch - 1);
-    uint2 raw[4];
-    raw[0] = bf_load((const char *) sp, spitch, x0, y0);
-    raw[1] = bf_load((const char *) sp, spitch, x1, y0);
-    raw[2] = bf_load((const char *) sp, spitch, x0, y1);
-    raw[3] = bf_load((const char *) sp, spitch, x1, y1);
-    // weights of the cell's columns and rows; a cell that sticks out of the rect (the padded
-    // first one, an odd size's last one) takes both from the pixel that exists
-    // (columns: one 8-byte load -- the table is padded by one entry at either end, which repeat the
-    // first / last weight; rows: uniform per wave, so scalar loads)
-    const plh_u32x2 axw = *(BF_GLOBAL const plh_u32x2 *) (colw + (size_t) (idx0 + 1) * 4);
-    const float ax[2] = { __uint_as_float(axw.x), __uint_as_float(axw.y) };
-    typedef __attribute__((address_space(4))) const float cfloat;
-    const float ay[2] = { ((cfloat *) roww)[idy0 + 1], ((cfloat *) roww)[idy0 + 2] };
-    float bias[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-    if (has_dither) {
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int ix = (idx0 + (q & 1) + fx0) & dmask;
-            const int iy = (idy0 + (q >> 1) + fy0) & dmask;
-            bias[q] = ((gfloat *) dmat)[iy * dsize + ix];
-        }
-    }
-
-    float t[4][NCH];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const uint32_t w[4] = { raw[k].x & 0xffff, raw[k].x >> 16, raw[k].y & 0xffff, raw[k].y >> 16 };
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++)
-            t[k][ch] = F16SRC ? plh_h2f(w[ch]) : plh_un16(w[ch]);
-    }
-    float4_t o[4];
-#pragma unroll
-    for (int ch = 0; ch < NCH; ch++) {
-        float top[2], bot[2];
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-            top[i] = plh_mix(t[0][ch], t[1][ch], ax[i]);
-            bot[i] = plh_mix(t[2][ch], t[3][ch], ax[i]);
-        }
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const float v = sscale * plh_mix(top[q & 1], bot[q & 1], ay[q >> 1]);
-            if (ch == 0) o[q].x = v;
-            if (ch == 1) o[q].y = v;
-            if (ch == 2) o[q].z = v;
-            if (ch == 3) o[q].w = v;
-        }
-    }
-    // epilogue: op_dither (plain path) + the SCALE op as in k_bilinear_fast. An alpha the plane
-    // does not carry is a constant; when it is 1 (video) it stays one behind dither and scale --
-    // floor(ds * 1 + b) == ds for every b in [0, 1) -- and is packed once per lane.
-        const bool alpha_one = RGB && alpha == 1.0f;
-    float aw = 1.0f;
-    if (has_dither)
-        aw = ds * di;
-    if (has_scale)
-        aw *= sc;
-    const uint32_t awbits = plh_unorm16x2(0.0f, aw) & 0xffff0000u;
-    uint2 px[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        if (RGB)
-            o[q].w = alpha;
-        if (has_dither) {
-            const float b = bias[q];
-            o[q].x = __builtin_floorf(ds * o[q].x + b) * di;
-            o[q].y = __builtin_floorf(ds * o[q].y + b) * di;
-            o[q].z = __builtin_floorf(ds * o[q].z + b) * di;
-            if (!alpha_one)
-                o[q].w = __builtin_floorf(ds * o[q].w + b) * di;
-        }
-        if (has_scale) {
-            o[q].x *= sc; o[q].y *= sc; o[q].z *= sc;
-            if (!alpha_one)
-                o[q].w *= sc;
-        }
-        px[q].x = plh_unorm16x2(o[q].x, o[q].y);
-        px[q].y = alpha_one ? ((plh_unorm16x2(o[q].z, 0.0f) & 0xffffu) | awbits) : plh_unorm16x2(o[q].z, o[q].w);
-    }
-    // the cell's two rows: both pixels in one 16-byte store where both exist
-    const int ox0 = bx + dirx * idx0, ox1 = bx + dirx * (idx0 + 1);
-    const bool okx0 = idx0 >= 0 && ox0 >= 0 && ox0 < dw, okx1 = idx0 + 1 < W && ox1 >= 0 && ox1 < dw;
-    typedef BF_GLOBAL plh_u32x2 gpair;
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const int idy = idy0 + j, oy = by + diry * idy;
-        if (idy < 0 || idy >= H || oy < 0 || oy >= dh)
-            continue;
-        const uintptr_t row = dptr + (size_t) oy * (size_t) dpitch;
-        const uint2 a = px[2 * j], b = px[2 * j + 1];
-        if (okx0 && okx1 && ox1 == ox0 + 1) {
-            // (a cell on an odd column is 8-byte aligned only: fine for global_store_dwordx4,
-            // which asks for dword alignment; the type says so. Two 8-byte streaming stores
-            // instead were slower here: 28.2 against 23.4 us.)
-            typedef plh_u32x4 __attribute__((aligned(8))) quad8;
-            const quad8 pk = { a.x, a.y, b.x, b.y };
-            if (nt)
-                __builtin_nontemporal_store(pk, (BF_GLOBAL quad8 *) (row + (size_t) ox0 * 8));
-            else {
-                *(BF_GLOBAL quad8 *) (row + (size_t) ox0 * 8) = pk;
-                PLH_KEEP_APART();
-            }
-            continue;
-        }
-        const plh_u32x2 lo = { a.x, a.y }, hi = { b.x, b.y };
-        if (okx0) {
-            if (nt) __builtin_nontemporal_store(lo, (gpair *) (row + (size_t) ox0 * 8));
-            else { *(gpair *) (row + (size_t) ox0 * 8) = lo; PLH_KEEP_APART(); }
-        }
-        if (okx1) {
-            if (nt) __builtin_nontemporal_store(hi, (gpair *) (row + (size_t) ox1 * 8));
-            else { *(gpair *) (row + (size_t) ox1 * 8) = hi; PLH_KEEP_APART(); }
-        }
-    }
-}
-
-/*
- * k_bilinear_strip (round 6): the 2x bilinear upscale as a stream -- ONE 16-byte load per 2 x 2
- * output cell. k_bilinear_fast and k_bilinear_tab fetch the four texels of every cell (four
- * 8-byte gathers per lane) and recompute, or look up, the geometry per cell; but with the geometry
- * proven separable (k_bilinear_tab_build: zero deviating pixels, base texel = b0 + cell index on
- * both axes) a column of cells is a sliding window down the source: cell row cy blends source rows
- * (b0y + cy, b0y + cy + 1), the next one (b0y + cy + 1, b0y + cy + 2). A wave owns 64 cell columns
- * and BS_ROWS consecutive cell rows: it requests the BS_ROWS + 1 source rows it needs at once (the
- * lane's two texels x0, x0 + 1 as one 16-byte load each: all of a wave's memory parallelism up
- * front), decodes and blends each row horizontally ONCE (it is the bottom row of one cell and the
- * top row of the next), and per cell does the vertical blends, the epilogue and two 16-byte
- * non-temporal stores. The lane's column weights live in registers for the whole strip, the row
- * weights are scalar loads. Arithmetic: k_bilinear_tab's statement for statement, i.e.
- * k_bilinear_fast's bit for bit (tests/test_gpu_kernel_variants.py). Per cell ~90 vector
- * instructions where k_bilinear_fast has ~330 -- and the memory shape of the bare 2x expand that
- * profiles/r02_hbm_rate.txt measured at 12.7 us.
- * MEASURED (profiles/r06_11_strip_ab.txt, r06_12_strip_rows.txt): 20.2 us in the trace at two cell
- * rows per wave, 24.0 / 23.8 at four / eight, k_bilinear_fast 19.0 on the same box. A third of the
- * instructions and a quarter of the load instructions bought nothing: the pass is bound by how
- * many bytes its waves keep in flight, and a wave that waits for ALL its rows before its first
- * store keeps fewer than four waves that each wait for one cell. Opt-in (PL_HIP_BILIN_STRIP=1),
- * kept as the record of the experiment VERDICT r05 item 6 asked for.
- */
-#define BS_ROWS_DEFAULT 2      // (20.2 us; 4: 24.0, 8: 23.8 -- profiles/r06_12_strip_rows.txt)
-// (blockDim.y waves per workgroup, each with its own strip; launched with one: four gained nothing)
-template <bool F16SRC, bool RGB, int BS_ROWS>
-__global__ __launch_bounds__(256)
-void k_bilinear_strip(const plh_pass p_, const float *colw_, const float *roww_, int b0x, int b0y)
-{
-    const plh_pass &p = plh_kernarg_pass();
-    const plh_sampler_args &s = p.s;
-    constexpr int NCH = RGB ? 3 : 4;
-    int W = p.width, H = p.height, padx = p.cell_padx, pady = p.cell_pady;
-    int spitch = s.src.pitch, srcw = s.src.w, srch = s.src.h;
-    int dmask = p.epi.mask, dsize = p.epi.size, has_dither = p.epi.has_dither, has_scale = p.epi.has_scale;
-    int fx0 = p.frag_x0, fy0 = p.frag_y0, bx = p.base_x, by = p.base_y, dirx = p.dir_x, diry = p.dir_y;
-    int dw = p.dst.w, dh = p.dst.h, dpitch = p.dst.pitch;
-    float ds = p.epi.dscale, di = p.epi.dinv, sc = p.epi.scale, alpha = p.epi.alpha, sscale = s.scale;
-    uintptr_t sp = (uintptr_t) s.src.ptr, dmat = (uintptr_t) p.epi.matrix, dptr = (uintptr_t) p.dst.ptr;
-    uintptr_t colw = (uintptr_t) colw_, roww = (uintptr_t) roww_;
-    asm volatile("" : "+s"(W), "+s"(H), "+s"(padx), "+s"(pady), "+s"(spitch), "+s"(srcw), "+s"(srch),
-                      "+s"(dmask), "+s"(dsize), "+s"(has_dither), "+s"(has_scale), "+s"(fx0), "+s"(fy0));
-    asm volatile("" : "+s"(bx), "+s"(by), "+s"(dirx), "+s"(diry), "+s"(dw), "+s"(dh), "+s"(dpitch),
-                      "+s"(ds), "+s"(di), "+s"(sc), "+s"(alpha), "+s"(sscale));
-    asm volatile("" : "+s"(sp), "+s"(dmat), "+s"(dptr), "+s"(colw), "+s"(roww), "+s"(b0x), "+s"(b0y));
-    typedef BF_GLOBAL const float gfloat;
-    typedef __attribute__((address_space(4))) const float cfloat;
-
-    const int cx = blockIdx.x * 64 + threadIdx.x;
-    const int cy0 = (blockIdx.y * blockDim.y + threadIdx.y) * BS_ROWS;
-    const int idx0 = 2 * cx - padx;
-    if (idx0 >= W)
-        return;
-    // the lane's two texels of a row: x0 = clamp(b), x1 = clamp(b + 1) as ONE 16-byte load at
-    // clamp(b, 0, w - 2); beyond the left edge both are the pair's first, beyond the right edge its
-    // second (the launcher requires a source at least two texels wide)
-    const int b = b0x + cx;
-    const int pcol = min(max(b, 0), srcw - 2);
-    const bool ldup = b < 0, hdup = b > srcw - 2;
-    typedef BF_GLOBAL const plh_u32x4 __attribute__((aligned(8))) gquad;
-    plh_u32x4 raw[BS_ROWS + 1];
-#pragma unroll
-    for (int k = 0; k <= BS_ROWS; k++) {
-        const int y = min(max(b0y + cy0 + k, 0), srch - 1);
-        raw[k] = *(gquad *) (sp + (size_t) y * (size_t) spitch + (size_t) pcol * 8);
-    }
-    // weights of the cell's columns (one 8-byte load; the table is padded by one entry at either
-    // end, which repeat the first / last weight)
-    const plh_u32x2 axw = *(BF_GLOBAL const plh_u32x2 *) (colw + (size_t) (idx0 + 1) * 4);
-    const float ax[2] = { __uint_as_float(axw.x), __uint_as_float(axw.y) };
-    const int ox0 = bx + dirx * idx0, ox1 = bx + dirx * (idx0 + 1);
-    const bool okx0 = idx0 >= 0 && ox0 >= 0 && ox0 < dw, okx1 = idx0 + 1 < W && ox1 >= 0 && ox1 < dw;
-    const bool alpha_one = RGB && alpha == 1.0f;
-    float aw = 1.0f;
-    if (has_dither)
-        aw = ds * di;
-    if (has_scale)
-        aw *= sc;
-    const uint32_t awbits = plh_unorm16x2(0.0f, aw) & 0xffff0000u;
-
-    // a source row, decoded and blended horizontally for the cell's two columns
-    auto hblend = [&](plh_u32x4 v, float (&h)[2][NCH]) {
-        if (ldup) { v.z = v.x; v.w = v.y; }
-        if (hdup) { v.x = v.z; v.y = v.w; }
-        const uint32_t w0[4] = { v.x & 0xffff, v.x >> 16, v.y & 0xffff, v.y >> 16 };
-        const uint32_t w1[4] = { v.z & 0xffff, v.z >> 16, v.w & 0xffff, v.w >> 16 };
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++) {
-            const float t0 = F16SRC ? plh_h2f(w0[ch]) : plh_un16(w0[ch]);
-            const float t1 = F16SRC ? plh_h2f(w1[ch]) : plh_un16(w1[ch]);
-            h[0][ch] = plh_mix(t0, t1, ax[0]);
-            h[1][ch] = plh_mix(t0, t1, ax[1]);
-        }
-    };
-    // Every row has ARRIVED before the first store is issued: gfx950 retires vector loads and stores
-    // through one in-order counter, and the stores below sit behind guards -- waiting for row k + 2
-    // behind the stores of cell k would be a wait for those stores (23.8 us against k_bilinear_fast's
-    // 19.0 when the rows were left to be waited for one by one: profiles/r06_11_strip_ab.txt).
-#pragma unroll
-    for (int k = 0; k <= BS_ROWS; k++)
-        asm volatile("" : "+v"(raw[k].x), "+v"(raw[k].y), "+v"(raw[k].z), "+v"(raw[k].w));
-    float top[2][NCH], bot[2][NCH];
-    hblend(raw[0], top);
-#pragma unroll
-    for (int k = 0; k < BS_ROWS; k++) {
-        const int cy = cy0 + k, idy0 = 2 * cy - pady;
-        if (idy0 >= H)
-            break;      // (uniform)
-        hblend(raw[k + 1], bot);
-        const float ay[2] = { ((cfloat *) roww)[idy0 + 1], ((cfloat *) roww)[idy0 + 2] };
-        float bias[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-        if (has_dither) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const int ix = (idx0 + (q & 1) + fx0) & dmask;
-                const int iy = (idy0 + (q >> 1) + fy0) & dmask;
-                bias[q] = ((gfloat *) dmat)[iy * dsize + ix];
-            }
-        }
-        float4_t o[4];
-#pragma unroll
-        for (int ch = 0; ch < NCH; ch++) {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float v = sscale * plh_mix(top[q & 1][ch], bot[q & 1][ch], ay[q >> 1]);
-                if (ch == 0) o[q].x = v;
-                if (ch == 1) o[q].y = v;
-                if (ch == 2) o[q].z = v;
-                if (ch == 3) o[q].w = v;
-            }
-        }
-        // epilogue: op_dither (plain path) + the SCALE op, as k_bilinear_tab
-        uint2 px[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (RGB)
-                o[q].w = alpha;
-            if (has_dither) {
-                const float bq = bias[q];
-                o[q].x = __builtin_floorf(ds * o[q].x + bq) * di;
-                o[q].y = __builtin_floorf(ds * o[q].y + bq) * di;
-                o[q].z = __builtin_floorf(ds * o[q].z + bq) * di;
-                if (!alpha_one)
-                    o[q].w = __builtin_floorf(ds * o[q].w + bq) * di;
-            }
-            if (has_scale) {
-                o[q].x *= sc; o[q].y *= sc; o[q].z *= sc;
-                if (!alpha_one)
-                    o[q].w *= sc;
-            }
-            px[q].x = plh_unorm16x2(o[q].x, o[q].y);
-            px[q].y = alpha_one ? ((plh_unorm16x2(o[q].z, 0.0f) & 0xffffu) | awbits) : plh_unorm16x2(o[q].z, o[q].w);
-        }
-        // the cell's two rows: both pixels in one 16-byte non-temporal store where both exist (the
-        // fused epilogue's target is a final rgba16 frame)
-        typedef BF_GLOBAL plh_u32x2 gpair;
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int idy = idy0 + j, oy = by + diry * idy;
-            if (idy < 0 || idy >= H || oy < 0 || oy >= dh)
-                continue;
-            const uintptr_t row = dptr + (size_t) oy * (size_t) dpitch;
-            const uint2 a = px[2 * j], c = px[2 * j + 1];
-            if (okx0 && okx1 && ox1 == ox0 + 1) {
-                typedef plh_u32x4 __attribute__((aligned(8))) quad8;
-                const quad8 pk = { a.x, a.y, c.x, c.y };
-                __builtin_nontemporal_store(pk, (BF_GLOBAL quad8 *) (row + (size_t) ox0 * 8));
-                continue;
-            }
-            const plh_u32x2 lo = { a.x, a.y }, hi = { c.x, c.y };
-            if (okx0)
-                __builtin_nontemporal_store(lo, (gpair *) (row + (size_t) ox0 * 8));
-            if (okx1)
-                __builtin_nontemporal_store(hi, (gpair *) (row + (size_t) ox1 * 8));
-        }
-#pragma unroll
-        for (int i = 0; i < 2; i++) {
-#pragma unroll
-            for (int ch = 0; ch < NCH; ch++)
-                top[i][ch] = bot[i][ch];
-        }
-    }
-}
-
-// The tables of a geometry, built and proven on first use (one launch + one read-back) and kept
-// for the life of the process: a handful of geometries per application.
-#include <mutex>
-struct bl_key {
-    int dev, src_w, src_h, width, height, padx, pady;
-    float pos[4][2];
-};
-struct bl_slot {
-    bl_key key;
-    bl_entry *cols, *rows;      // device; NULL: the geometry is not separable (k_bilinear_fast)
-    float *colw, *roww;         // the weights alone (what the frame kernel reads)
-    int b0x, b0y;               // base texel of column X / row Y = b0 + ((X + pad) >> 1)
-    bool used;
-};
-static bl_slot g_bl_slots[8];
-static unsigned g_bl_next;
-static std::mutex g_bl_mutex;
-
-static const bl_slot *bilinear_tables(hipStream_t stream, const plh_pass *pass)
-{
-    // OFF unless asked for: with 36 % fewer vector instructions than k_bilinear_fast (7.0 M against
-    // 11.0 M per 4K frame, same 33.6 k waves) this kernel is SLOWER -- 23.4 us against 18.5-19.5
-    // (profiles/r04_12_bilinear_tables.txt: addresses from the tables 27 us, from the cell index
-    // with every load issued at once 23.8, weights as one 8-byte + two scalar loads 23.4, two
-    // 8-byte streaming stores 28.2). The pass is not bound by VALU issue after all; VERDICT r03
-    // item 6 asked for this experiment and for the item to be closed if it lost. It is kept
-    // selectable (PL_HIP_BILIN_TABLES=1) because its frames are proven identical and it is the
-    // record of the measurement.
-    // (round 6: the tables are also what k_bilinear_strip runs on, PL_HIP_BILIN_STRIP=1 -- it lost as
-    // well: 20.2 us in the trace with two cell rows per wave, 24.0 / 23.8 with four / eight, against
-    // k_bilinear_fast's 19.0 on the same box, profiles/r06_11_strip_ab.txt, r06_12_strip_rows.txt)
-    const bool want_tab = plh_switch(PLH_SW_BILIN_TABLES) == 1, want_strip = plh_switch(PLH_SW_BILIN_STRIP) == 1;
-    if (!want_tab && !(want_strip && pass->s.src.w >= 2 && pass->dst.fmt == PLH_FMT_RGBA16))
-        return nullptr;
-    bl_key key = {};
-    key.dev = plh_stream_device((plh_stream) stream, nullptr);
-    key.src_w = pass->s.src.w; key.src_h = pass->s.src.h;
-    key.width = pass->width; key.height = pass->height;
-    key.padx = pass->cell_padx; key.pady = pass->cell_pady;
-    memcpy(key.pos, pass->s.pos, sizeof(key.pos));
-    std::lock_guard<std::mutex> lock(g_bl_mutex);
-    for (const bl_slot &sl : g_bl_slots) {
-        if (sl.used && !memcmp(&sl.key, &key, sizeof(key)))
-            return sl.cols ? &sl : nullptr;
-    }
-    bl_slot &sl = g_bl_slots[g_bl_next++ % 8];
-    if (sl.used && sl.cols) {
-        (void) hipFree(sl.cols);    // (synchronises: nothing in flight reads an evicted table)
-    }
-    sl = bl_slot{};
-    sl.key = key;
-    sl.used = true;
-    const int W = pass->width, H = pass->height;
-    const size_t bytes = ((size_t) W + H) * sizeof(bl_entry) + 16, wbytes = ((size_t) W + H + 4) * sizeof(float);
-    char *dev = nullptr;
-    int cur = key.dev;
-    (void) hipGetDevice(&cur);
-    if (cur != key.dev)
-        (void) hipSetDevice(key.dev);
-    bool ok = hipMalloc((void **) &dev, bytes + wbytes) == hipSuccess;
-    if (cur != key.dev)
-        (void) hipSetDevice(cur);
-    if (!ok)
-        return nullptr;
-    bl_entry *cols = (bl_entry *) dev, *rows = cols + W;
-    uint32_t *count = (uint32_t *) (rows + H);
-    float *colw = (float *) (dev + bytes), *roww = colw + W + 2;
-    ok = hipMemsetAsync(count, 0, 4, stream) == hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(k_bilinear_tab_build, dim3((W + 63) / 64, (H + 3) / 4), dim3(256), 0, stream,
-                           *pass, cols, rows, count, colw, roww);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    std::vector<bl_entry> host((size_t) W + H + 2);
-    ok = ok && hipMemcpyAsync(host.data(), dev, bytes, hipMemcpyDeviceToHost, stream) == hipSuccess &&
-         hipStreamSynchronize(stream) == hipSuccess;
-    uint32_t deviating = 1;
-    if (ok)
-        memcpy(&deviating, &host[(size_t) W + H], 4);
-    // the base texel advances by one per cell: base(X) = b0 + ((X + pad) >> 1) on both axes (a 2x
-    // upscale on the cell phase the dispatch chose; anything else keeps the per-pixel kernel)
-    ok = ok && deviating == 0;
-    const int b0x = ok ? host[0].base - (key.padx >> 1) : 0, b0y = ok ? host[W].base - (key.pady >> 1) : 0;
-    for (int x = 0; ok && x < W; x++)
-        ok = host[x].base == b0x + ((x + key.padx) >> 1);
-    for (int y = 0; ok && y < H; y++)
-        ok = host[W + y].base == b0y + ((y + key.pady) >> 1);
-    if (!ok) {
-        (void) hipFree(dev);
-        return nullptr;     // (remembered: sl.cols == NULL)
-    }
-    sl.cols = cols;
-    sl.rows = rows;
-    sl.colw = colw;
-    sl.roww = roww;
-    sl.b0x = b0x;
-    sl.b0y = b0y;
-    return &sl;
-}
-
-template <bool F16SRC>
-static void launch_bilinear_tab(hipStream_t stream, const plh_pass *pass, const bl_slot *tab)
-{
-    const int cells_w = (pass->width + pass->cell_padx + 1) / 2;
-    const int cells_h = (pass->height + pass->cell_pady + 1) / 2;
-    if (plh_switch(PLH_SW_BILIN_TABLES) != 1) {
-        // the strip kernel: a wave per 64 cell columns x BS_ROWS_DEFAULT cell rows
-        const dim3 sgrid((cells_w + 63) / 64, (cells_h + BS_ROWS_DEFAULT - 1) / BS_ROWS_DEFAULT);
-        if (pass->epi.has_alpha)
-            PLH_LAUNCH_LAST((k_bilinear_strip<F16SRC, true, BS_ROWS_DEFAULT>), sgrid, dim3(64), 0, stream, *pass, tab->colw, tab->roww, tab->b0x, tab->b0y);
-        else
-            PLH_LAUNCH_LAST((k_bilinear_strip<F16SRC, false, BS_ROWS_DEFAULT>), sgrid, dim3(64), 0, stream, *pass, tab->colw, tab->roww, tab->b0x, tab->b0y);
-        return;
-    }
-    const dim3 block(BF_BW, BF_BH), grid((cells_w + BF_BW - 1) / BF_BW, (cells_h + BF_BH - 1) / BF_BH);
-    if (pass->epi.has_alpha)
-        PLH_LAUNCH_LAST((k_bilinear_tab<F16SRC, true>), grid, block, 0, stream, *pass, tab->colw, tab->roww, tab->b0x, tab->b0y);
-    else
-        PLH_LAUNCH_LAST((k_bilinear_tab<F16SRC, false>), grid, block, 0, stream, *pass, tab->colw, tab->roww, tab->b0x, tab->b0y);
-}
-
 /* ------------------------------------------------------------------------ */
 
 int plh_launch_polar(hipStream_t stream, const plh_pass *pass);
@@ -1477,9 +958,7 @@ static int plh_launch_generic(hipStream_t stream, const plh_pass *pass, bool cub
     // 2x2 cells share the bilinear footprint; everything else prefers the lighter 2x1 cells
     // (measured: 4K colour map 193 -> 168 us, plane copy 20.4 -> 18.8 us)
     int ch = pass->s.type == PLH_SAMPLE_BILINEAR && lite ? 2 : 1;
-    bool mixing = false;
-    for (int i = 0; i < pass->num_ops; i++)
-        mixing |= pass->ops[i].kind == PLH_OP_MIX_ADD;
+    const bool mixing = plh_pass_has_op(pass, PLH_OP_MIX_ADD);
     if (mixing || cubic || dovi)
         ch = 1;
     const int cells_w = (pass->width + pass->cell_padx + 1) / 2;
@@ -1510,9 +989,27 @@ static int plh_launch_generic(hipStream_t stream, const plh_pass *pass, bool cub
         else                LAUNCH(false, false, 1);
     }
 #undef LAUNCH
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }
+
+// grid of the kernels that give a lane two horizontally adjacent pixels of a 1:1 pass, in
+// workgroups of PASS_BW x PASS_BH lanes (k_pass_merge, k_pass_mix, k_pass_features)
+static dim3 pass_pair_grid(const plh_pass *pass)
+{
+    return dim3(((pass->width + 1) / 2 + PASS_BW - 1) / PASS_BW, (pass->height + PASS_BH - 1) / PASS_BH);
+}
+
+// A specialised kernel with a <true> / <false> pair of instances, once its test has passed: name it
+// in the trace, launch the instance `which` picks as the pass's last kernel and return the status.
+#define PASS_RETURN_LAUNCH(kernel, which, grid, block, ...)                                         \
+    do {                                                                                            \
+        plh_trace_kernel(#kernel);                                                                  \
+        if (which)                                                                                  \
+            PLH_LAUNCH_LAST(kernel<true>, grid, block, 0, stream, __VA_ARGS__);                     \
+        else                                                                                        \
+            PLH_LAUNCH_LAST(kernel<false>, grid, block, 0, stream, __VA_ARGS__);                    \
+        return plh_launch_status();                                                                 \
+    } while (0)
 
 extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
 {
@@ -1529,17 +1026,16 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
         fprintf(stderr, "\n");
     }
 
+    const bool measuring = plh_pass_has_op(pass, PLH_OP_PEAK_DETECT);
+    const bool mixing = plh_pass_has_op(pass, PLH_OP_MIX_ADD);
+
     // lut3d_tricubic lives in one variant of the generic kernel: such a colour map must be its
     // own pass (the renderer arranges that; a hand-built shader samples from an FBO first)
-    bool cubic = false;
-    for (int i = 0; i < pass->num_ops; i++)
-        cubic |= pass->ops[i].kind == PLH_OP_GAMUT_LUT && pass->ops[i].f[3] != 0.0f;
+    const bool cubic = pass_has_tricubic(pass);
     if (cubic) {
-        bool alone = pass->s.type == PLH_SAMPLE_NONE || pass->s.type == PLH_SAMPLE_NEAREST ||
-                     pass->s.type == PLH_SAMPLE_BILINEAR;
-        for (int i = 0; i < pass->num_ops; i++)
-            alone &= pass->ops[i].kind != PLH_OP_PEAK_DETECT && pass->ops[i].kind != PLH_OP_MIX_ADD;
-        if (!alone)
+        const bool simple = pass->s.type == PLH_SAMPLE_NONE || pass->s.type == PLH_SAMPLE_NEAREST ||
+                            pass->s.type == PLH_SAMPLE_BILINEAR;
+        if (!simple || measuring || mixing)
             return -1004;
     }
 
@@ -1557,10 +1053,8 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
         viz |= plh_op_is_viz(pass->ops[i].kind);
     }
     if (dovi) {
-        for (int i = 0; i < pass->num_ops; i++) {
-            if (pass->ops[i].kind == PLH_OP_PEAK_DETECT || (viz && pass->ops[i].kind == PLH_OP_MIX_ADD))
-                return -1004;
-        }
+        if (measuring || (viz && mixing))
+            return -1004;
         if (pass->s.type >= PLH_SAMPLE_POLAR && pass->s.type != PLH_SAMPLE_DISTORT)
             return -1004;
         if (viz)
@@ -1578,105 +1072,60 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
     case PLH_SAMPLE_DEINTERLACE:
         // (its kernel carries the plain interpreter: a measurement, a frame mix or the tricubic
         // LUT behind it need the deinterlaced plane as a texture first, as the renderer arranges)
-        for (int i = 0; i < pass->num_ops; i++) {
-            if (pass->ops[i].kind == PLH_OP_PEAK_DETECT || pass->ops[i].kind == PLH_OP_MIX_ADD)
-                return -1004;
-        }
-        return cubic ? -1004 : plh_launch_deinterlace(stream_, pass);
+        return measuring || mixing || cubic ? -1004 : plh_launch_deinterlace(stream_, pass);
     default:
         break;
     }
 
     // a peak-detection stage needs the 16x16 tiling + LDS state of k_peak.hip
-    for (int i = 0; i < pass->num_ops; i++) {
-        if (pass->ops[i].kind == PLH_OP_PEAK_DETECT)
-            return plh_launch_peak(stream, pass);
-    }
+    if (measuring)
+        return plh_launch_peak(stream, pass);
 
+    // The specialised kernels, in the order they are tried. Each matches on a copy of the pass,
+    // which its `*_applies` test fills in (epi, chain) for its kernel alone.
     {
         plh_pass local = *pass;
         if (nearest_fast_ok(&local)) {
-            plh_trace_kernel("k_nearest_fast");
             const int cells_w = (local.width + local.cell_padx + 1) / 2;
-            const dim3 block(BF_BW, BF_BH);
             const dim3 grid((cells_w + BF_BW - 1) / BF_BW,
                             (local.height + BF_BH * NF_ROWS - 1) / (BF_BH * NF_ROWS));
-            if (local.s.src.fmt == PLH_FMT_RGBA16F)
-                PLH_LAUNCH_LAST(k_nearest_fast<true>, grid, block, 0, stream, local);
-            else
-                PLH_LAUNCH_LAST(k_nearest_fast<false>, grid, block, 0, stream, local);
-            const hipError_t err = hipGetLastError();
-            return err == hipSuccess ? 0 : -(int) err;
+            PASS_RETURN_LAUNCH(k_nearest_fast, local.s.src.fmt == PLH_FMT_RGBA16F,
+                               grid, dim3(BF_BW, BF_BH), local);
         }
     }
 
     {
         plh_pass local = *pass;
         const int iters = bilinear_fast_iters(&local);
-        const bl_slot *tab = iters ? bilinear_tables(stream, &local) : nullptr;
-        if (tab) {
-            plh_trace_kernel("k_bilinear_tab");
-            if (local.s.src.fmt == PLH_FMT_RGBA16F)
-                launch_bilinear_tab<true>(stream, &local, tab);
-            else
-                launch_bilinear_tab<false>(stream, &local, tab);
-            const hipError_t err = hipGetLastError();
-            return err == hipSuccess ? 0 : -(int) err;
-        }
         if (iters) {
             plh_trace_kernel("k_bilinear_fast");
             if (local.s.src.fmt == PLH_FMT_RGBA16F)
                 launch_bilinear_fast<true>(stream, &local, iters);
             else
                 launch_bilinear_fast<false>(stream, &local, iters);
-            const hipError_t err = hipGetLastError();
-            return err == hipSuccess ? 0 : -(int) err;
+            return plh_launch_status();
         }
     }
 
     {
         plh_pass local = *pass;
         plh_merge m;
-        if (pass_merge_applies(&local, &m)) {
-            plh_trace_kernel("k_pass_merge");
-            const dim3 block(PASS_BW, PASS_BH);
-            const dim3 grid(((local.width + 1) / 2 + PASS_BW - 1) / PASS_BW, (local.height + PASS_BH - 1) / PASS_BH);
-            if (local.dst.fmt == PLH_FMT_RGBA16F)
-                PLH_LAUNCH_LAST(k_pass_merge<true>, grid, block, 0, stream, local, m);
-            else
-                PLH_LAUNCH_LAST(k_pass_merge<false>, grid, block, 0, stream, local, m);
-            const hipError_t err = hipGetLastError();
-            return err == hipSuccess ? 0 : -(int) err;
-        }
+        if (pass_merge_applies(&local, &m))
+            PASS_RETURN_LAUNCH(k_pass_merge, local.dst.fmt == PLH_FMT_RGBA16F,
+                               pass_pair_grid(&local), dim3(PASS_BW, PASS_BH), local, m);
     }
 
     {
         plh_pass local = *pass;
         plh_mixplan mp;
-        if (pass_mix_applies(&local, &mp)) {
-            plh_trace_kernel("k_pass_mix");
-            const dim3 block(PASS_BW, PASS_BH);
-            const dim3 grid(((local.width + 1) / 2 + PASS_BW - 1) / PASS_BW, (local.height + PASS_BH - 1) / PASS_BH);
-            if (local.dst.fmt == PLH_FMT_RGBA16F)
-                PLH_LAUNCH_LAST(k_pass_mix<true>, grid, block, 0, stream, local, mp);
-            else
-                PLH_LAUNCH_LAST(k_pass_mix<false>, grid, block, 0, stream, local, mp);
-            const hipError_t err = hipGetLastError();
-            return err == hipSuccess ? 0 : -(int) err;
-        }
+        if (pass_mix_applies(&local, &mp))
+            PASS_RETURN_LAUNCH(k_pass_mix, local.dst.fmt == PLH_FMT_RGBA16F,
+                               pass_pair_grid(&local), dim3(PASS_BW, PASS_BH), local, mp);
     }
 
-    if (pass_native_applies(pass, true)) {
-        plh_trace_kernel("k_pass_features");
-        const dim3 block(PASS_BW, PASS_BH);
-        const dim3 grid(((pass->width + 1) / 2 + PASS_BW - 1) / PASS_BW, (pass->height + PASS_BH - 1) / PASS_BH);
-        if (pass->s.src.fmt == PLH_FMT_RGBA16F)
-            PLH_LAUNCH_LAST(k_pass_features<true>, grid, block, 0, stream, *pass);
-        else
-            PLH_LAUNCH_LAST(k_pass_features<false>, grid, block, 0, stream, *pass);
-        const hipError_t err = hipGetLastError();
-        return err == hipSuccess ? 0 : -(int) err;
-    }
+    if (pass_native_applies(pass, true))
+        PASS_RETURN_LAUNCH(k_pass_features, pass->s.src.fmt == PLH_FMT_RGBA16F,
+                           pass_pair_grid(pass), dim3(PASS_BW, PASS_BH), *pass);
 
     if (pass_native_applies(pass)) {
         plh_pass local = *pass;
@@ -1730,13 +1179,13 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
             launch_pass_native<true>(stream, pass);
         else
             launch_pass_native<false>(stream, pass);
-        const hipError_t err = hipGetLastError();
-        return err == hipSuccess ? 0 : -(int) err;
+        return plh_launch_status();
     }
 
     plh_trace_kernel("k_pass_generic");
     return plh_launch_generic(stream, pass, cubic, false);
 }
+#undef PASS_RETURN_LAUNCH
 
 // Test hook (tests/test_chain_match.py, CPU): plh_match_map_chain on an op list described by its
 // kinds and one flag word per op -- TONE_MAP: 1 = contrast recovery; GAMUT_LUT: 1 = tricubic;

@@ -18,6 +18,5 @@ int plh_launch_generic_viz(hipStream_t stream, const plh_pass *pass, bool cubic)
         PLH_LAUNCH_LAST((k_pass_generic<false, false, 1, false, true, true, true>), grid, block, 0, stream, *pass);
     else
         PLH_LAUNCH_LAST((k_pass_generic<false, false, 1, false, false, true, true>), grid, block, 0, stream, *pass);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

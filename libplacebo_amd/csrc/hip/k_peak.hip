@@ -948,8 +948,7 @@ int plh_launch_peak(hipStream_t stream, const plh_pass *pass)
         else if (store)         { if (pq) PEAK_TILES_GO(false, 1, true); else PEAK_TILES_GO(false, 1, false); }
         else                    { if (pq) PEAK_TILES_GO(false, 0, true); else PEAK_TILES_GO(false, 0, false); }
 #undef PEAK_TILES_GO
-        const hipError_t terr = hipGetLastError();
-        return terr == hipSuccess ? 0 : -(int) terr;
+        return plh_launch_status();
     }
     if (peak_fast_applies(pass)) {
         plh_trace_kernel("k_peak_fast");
@@ -973,6 +972,5 @@ int plh_launch_peak(hipStream_t stream, const plh_pass *pass)
                        dim3(FOLD_WORDS * FOLD_GROUPS), 0, stream, (uint32_t *) pass->peak_buf,
                        (uint32_t *) pass->peak_scratch, (uint32_t *) pass->peak_mailbox,
                        pass->peak_ticket);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

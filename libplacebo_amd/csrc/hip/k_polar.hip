@@ -288,8 +288,7 @@ int plh_launch_polar_classify(plh_stream stream, const plh_pass *pass, void *out
     const int n = pass->width > pass->height ? pass->width : pass->height;
     hipLaunchKernelGGL(k_polar_classify, dim3((n + 255) / 256), dim3(256), 0,
                        (hipStream_t) stream, *pass, (float *) out);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }
 
 int plh_launch_polar_weights(plh_stream stream, const plh_pass *pass, const float *clsx, int ncx,
@@ -297,8 +296,7 @@ int plh_launch_polar_weights(plh_stream stream, const plh_pass *pass, const floa
 {
     hipLaunchKernelGGL(k_polar_weights, dim3((ncx * ncy + 63) / 64), dim3(64), 0,
                        (hipStream_t) stream, *pass, clsx, ncx, clsy, ncy, weights);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }
 
 template <typename T, uint32_t MASK>
@@ -308,8 +306,7 @@ static int launch_ar(hipStream_t stream, const plh_pass *pass, dim3 grid, dim3 b
         PLH_LAUNCH_LAST((k_polar<T, MASK, true>), grid, block, shmem, stream, *pass);
     else
         PLH_LAUNCH_LAST((k_polar<T, MASK, false>), grid, block, shmem, stream, *pass);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }
 
 template <typename T>

@@ -458,6 +458,5 @@ int plh_launch_polar_mxd(hipStream_t stream, const plh_pass *pass)
     else if (f16dst)      MXD_LAUNCH(false, true, false, false);
     else                  MXD_LAUNCH(false, false, false, false);
 #undef MXD_LAUNCH
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

@@ -489,6 +489,5 @@ int plh_launch_polar_mxp(hipStream_t stream, const plh_pass *pass)
         launch_mxp<MXP_STORE_DEFAULT>(stream, pass, groups, shmem);
     else
         launch_mxp<0>(stream, pass, groups, shmem);
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

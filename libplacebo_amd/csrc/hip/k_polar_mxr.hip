@@ -402,6 +402,5 @@ int plh_launch_polar_mxr(hipStream_t stream, const plh_pass *pass)
     else
         return -1000;
 #undef MXR_LAUNCH
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

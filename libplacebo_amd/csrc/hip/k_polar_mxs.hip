@@ -6,8 +6,7 @@ static int launch_shape(hipStream_t stream, const plh_pass *pass)
 {
     if (!launch_mx_variant<3, true, POST, 8>(stream, pass))
         return 1;
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }
 
 int plh_launch_polar_mx_shape(hipStream_t stream, const plh_pass *pass, int shape)

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "backend.h"
+#include "devmath.hiph"     // (plh_launch_status)
 #include "plh_texel.h"
 
 template <int FMT>
@@ -154,6 +155,5 @@ extern "C" int plh_launch_texel_convert(plh_stream s, int texel_fmt, int pack, c
     case PLH_TEXEL_BGR10A2: launch_fmt<PLH_TEXEL_BGR10A2>((hipStream_t) s, pack, sp, src_pitch, dp, dst_pitch, w, h); break;
     default: return -(int) hipErrorInvalidValue;
     }
-    const hipError_t err = hipGetLastError();
-    return err == hipSuccess ? 0 : -(int) err;
+    return plh_launch_status();
 }

@@ -457,7 +457,7 @@ struct plh_pass {
     struct plh_distort_args distort;    // PLH_SAMPLE_DISTORT
 };
 
-/* host side: two shapes the specialised kernels' `*_applies` tests share */
+/* host side: what the launchers' `*_applies` tests share */
 // the pass covers its source 1:1: as large as it, `pos` = the unit square in the standard corner order
 static inline int plh_pass_covers_source(const struct plh_pass *pass)
 {
@@ -472,6 +472,16 @@ static inline int plh_pass_plain_target(const struct plh_pass *pass)
 {
     return pass->base_x == 0 && pass->base_y == 0 && pass->dir_x == 1 && pass->dir_y == 1 &&
            pass->dst.w >= pass->width && pass->dst.h >= pass->height;
+}
+
+// the op list holds an op of this kind
+static inline int plh_pass_has_op(const struct plh_pass *pass, int kind)
+{
+    for (int i = 0; i < pass->num_ops; i++) {
+        if (pass->ops[i].kind == kind)
+            return 1;
+    }
+    return 0;
 }
 
 /* ---- error diffusion (k_errdiff.hip) ------------------------------------------ */

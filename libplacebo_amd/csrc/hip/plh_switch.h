@@ -27,8 +27,6 @@ extern "C" {
     X(CHAIN_SHAPE,     "PL_HIP_CHAIN_SHAPE",      1, "0: k_polar_mx's generic chain instance always, instead of its shape-specialised one for HDR10 -> SDR passes (bit-identical)") \
     X(PASS_NATIVE,     "PL_HIP_PASS_NATIVE",      1, "0: 1:1 passes on k_pass_generic instead of k_pass_native / k_pass_chain / k_pass_merge / k_pass_mix") \
     X(BILIN_ITERS,     "PL_HIP_BILIN_ITERS",      1, "1 | 2 | 4 cells per lane of k_bilinear_fast; 0: k_pass_generic instead of it and of k_nearest_fast") \
-    X(BILIN_TABLES,    "PL_HIP_BILIN_TABLES",     0, "1: the 2x bilinear upscale on k_bilinear_tab (per-axis tables) instead of k_bilinear_fast") \
-    X(BILIN_STRIP,     "PL_HIP_BILIN_STRIP",      0, "1: the 2x bilinear upscale on k_bilinear_strip (a 16-byte load per cell) instead of k_bilinear_fast") \
     X(ORTHO_FAST,      "PL_HIP_ORTHO_FAST",       1, "0: separable passes on k_ortho instead of k_ortho_fast") \
     X(LOWPASS_FUSED,   "PL_HIP_LOWPASS_FUSED",    1, "0: the feature map's low-pass as two ortho passes instead of the one k_lowpass2 launch") \
     X(DEBAND_FAST,     "PL_HIP_DEBAND_FAST",      1, "0: debanding on k_deband instead of k_deband_fast / k_deband_lds") \

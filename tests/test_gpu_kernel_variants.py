@@ -60,54 +60,54 @@ def test_bilinear_fast_equals_generic(gpu, scale, ten_bit):
     assert outs[0][..., :3].std() > 1000
 
 
-@pytest.mark.parametrize("size", [((100, 58), (200, 116)), ((101, 59), (202, 118)), ((96, 64), (288, 128)),
-                                  ((1920, 1080), (3840, 2160))])
+def fast_and_generic(gpu, capfd, img, dw, dh, params, ten_bit, **kw):
+    """One frame on k_bilinear_fast (the default switches) and on k_pass_generic
+    (PL_HIP_BILIN_ITERS=0). The trace says which kernel took either render: the comparison
+    cannot pass by running one of them twice. k_bilinear_fast declines by the pass's shape alone
+    (bilinear_fast_iters, plh_match_fast_epilogue: sampler, addressing, formats, the op tail) and
+    never by its size, so it is expected at every size the callers use, 2 x 2 included."""
+    with util.kernel_trace(capfd) as k_fast:
+        fast = render(gpu, img, dw, dh, params, ten_bit, {}, **kw)
+    with util.kernel_trace(capfd, PL_HIP_BILIN_ITERS="0") as k_generic:
+        generic = render(gpu, img, dw, dh, params, ten_bit, {}, **kw)
+    assert k_fast == ["k_bilinear_fast"] and k_generic == ["k_pass_generic"], (k_fast, k_generic)
+    return fast, generic
+
+
+@pytest.mark.parametrize("size", [((100, 58), (200, 116)), ((101, 59), (202, 118)), ((96, 64), (288, 128))])
 @pytest.mark.parametrize("ten_bit", [False, True])
-def test_bilinear_tables_equal_per_pixel_geometry(gpu, size, ten_bit):
-    """k_bilinear_strip (round 6, opt-in -- it lost, profiles/r06_12_strip_rows.txt: one 16-byte load per
-    2 x 2 cell, a wave sliding down 64 cell columns) and k_bilinear_tab (geometry from per-column /
-    per-row tables; PL_HIP_BILIN_TABLES=1) against k_bilinear_fast (PL_HIP_BILIN_STRIP=0: per-pixel
-    attribute interpolation, floor, fract) and the generic kernel: the same frames bit for bit -- 2x
-    at even and odd sizes, 3x2 (where a cell's two columns do not share a texel: the tables decline
-    and every run is the per-pixel kernel), the BASELINE frame; rgba16hf source too."""
+def test_bilinear_fast_equals_generic_rgba16_and_f16_sources(gpu, capfd, size, ten_bit):
+    """k_bilinear_fast (per-pixel attribute interpolation, floor, fract; the four pixels of a cell
+    on one footprint where they share it) against the generic kernel: the same frames bit for bit
+    -- 2x at even and odd sizes, 3x2 (where a cell's two columns do not share a texel: every
+    pixel fetches its own footprint), out of an rgba16 and an rgba16hf source, with and without the
+    10-bit dither."""
     (sw, sh), (dw, dh) = size
     img = util.chirp_rgba16(sw, sh)
     kw = dict(dither_params=dither(), disable_dither_gamma_correction=True) if ten_bit else {}
     params = pl.render_params("fast", **kw)
-    per_px_env = {"PL_HIP_BILIN_STRIP": "0", "PL_HIP_BILIN_TABLES": "0"}
-    strip = render(gpu, img, dw, dh, params, ten_bit, {"PL_HIP_BILIN_STRIP": "1", "PL_HIP_BILIN_TABLES": "0"})
-    tab = render(gpu, img, dw, dh, params, ten_bit, {"PL_HIP_BILIN_TABLES": "1"})    # (opt-in: it lost, profiles/r04_12)
-    per_px = render(gpu, img, dw, dh, params, ten_bit, per_px_env)
-    assert np.array_equal(tab, per_px), util.diff_stats(tab, per_px)
-    assert np.array_equal(strip, per_px), util.diff_stats(strip, per_px)
-    if sw < 1000:
-        generic = render(gpu, img, dw, dh, params, ten_bit, {"PL_HIP_BILIN_ITERS": "0"})
-        assert np.array_equal(tab, generic)
-        f16 = (img.astype(np.float32) / 65535.0).astype(np.float16)
-        a = render(gpu, f16, dw, dh, params, ten_bit, {"PL_HIP_BILIN_TABLES": "1"}, src_fmt="rgba16hf")
-        b = render(gpu, f16, dw, dh, params, ten_bit, per_px_env, src_fmt="rgba16hf")
-        c = render(gpu, f16, dw, dh, params, ten_bit, {"PL_HIP_BILIN_STRIP": "1"}, src_fmt="rgba16hf")
-        assert np.array_equal(a, b) and np.array_equal(c, b)
-    assert tab[..., :3].std() > 1000
+    fast, generic = fast_and_generic(gpu, capfd, img, dw, dh, params, ten_bit)
+    assert np.array_equal(fast, generic), util.diff_stats(fast, generic)
+    f16 = (img.astype(np.float32) / 65535.0).astype(np.float16)
+    a, b = fast_and_generic(gpu, capfd, f16, dw, dh, params, ten_bit, src_fmt="rgba16hf")
+    assert np.array_equal(a, b), util.diff_stats(a, b)
+    assert fast[..., :3].std() > 1000
 
 
 @pytest.mark.parametrize("size", [(7, 5), (64, 9), (65, 8), (129, 17), (300, 170), (2, 2)])
-def test_bilinear_strip_odd_sizes_flips_and_alpha(gpu, size):
-    """k_bilinear_strip at sizes whose last wave / last strip are partial (a strip is 8 cell rows, a
-    wave 64 cell columns; the first cell of either axis is the padded one), a flipped source rect
-    (the tables decline: both runs are the per-pixel kernel) and a 10-bit dithered target, against
-    k_bilinear_fast: bit for bit."""
+def test_bilinear_fast_equals_generic_odd_sizes_flips_and_alpha(gpu, capfd, size):
+    """k_bilinear_fast at sizes whose last wave / last cell row are partial (a workgroup is 64 cell
+    columns by 4 cell rows; the first cell of either axis is the padded one), random frames, a
+    flipped source rect and a 10-bit dithered target, against the generic kernel: bit for bit."""
     sw, sh = size
     rng = np.random.default_rng(sw * 31 + sh)
     img = rng.integers(0, 65536, (sh, sw, 4), dtype=np.uint16)
     params = pl.render_params("fast")
     for crop in (None, (float(sw), float(sh), 0.0, 0.0)):      # (the second: a flipped source rect)
-        a = render(gpu, img, 2 * sw, 2 * sh, params, False, {"PL_HIP_BILIN_STRIP": "1"}, crop=crop)
-        b = render(gpu, img, 2 * sw, 2 * sh, params, False, {"PL_HIP_BILIN_STRIP": "0"}, crop=crop)
+        a, b = fast_and_generic(gpu, capfd, img, 2 * sw, 2 * sh, params, False, crop=crop)
         assert np.array_equal(a, b), util.diff_stats(a, b)
     params10 = pl.render_params("fast", dither_params=dither(), disable_dither_gamma_correction=True)
-    a = render(gpu, img, 2 * sw, 2 * sh, params10, True, {"PL_HIP_BILIN_STRIP": "1"})
-    b = render(gpu, img, 2 * sw, 2 * sh, params10, True, {"PL_HIP_BILIN_STRIP": "0"})
+    a, b = fast_and_generic(gpu, capfd, img, 2 * sw, 2 * sh, params10, True)
     assert np.array_equal(a, b), util.diff_stats(a, b)
 
 
