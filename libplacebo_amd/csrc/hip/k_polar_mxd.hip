@@ -33,7 +33,7 @@
  * DELINEARIZE in front of the fused epilogue (SDR 4K -> 1080p in linear light). Everything else
  * stays on k_polar_pp.
  */
-#include "polar_common.hiph"
+#include "mx_tile.hiph"
 #include "transfer.hiph"
 
 #define MXD_TW      64                      // output columns per workgroup tile
@@ -67,32 +67,17 @@ void k_polar_mxd(const plh_pass p_)
     unsigned char *bl = smem;
     unsigned char *tile = smem + MXD_B_BYTES;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // profiling aid (PL_HIP_PP_DEBUG: 1 = no contraction, 4 = no stores, 8 = no tile loads): only in a
-    // library built with -DPLH_MX_DEBUG (k_polar_mx.hiph says what the switches cost)
-#ifdef PLH_MX_DEBUG
-    const int dbg = s.pp_debug;
-#else
-    constexpr int dbg = 0;
-#endif
+    const int dbg = MX_DBG(s);      // (profiling aid, mx_tile.hiph)
     int j0 = mx.row_first[0];       // first source row with a weight (uniform)
     asm volatile("" : "+s"(j0));
 
     // Persistent workgroups, one per CU: the B fragments are loaded once, and the loads of the next
-    // tile are in flight (in registers) while this one is contracted. Workgroups go to the 8 XCDs
-    // round-robin and every XCD has its own L2: XCD x works on the x-th contiguous eighth of the
-    // tiles (row-major), its workgroups side by side on consecutive tiles -- neighbours share 12
-    // source rows / columns of halo.
+    // tile are in flight (in registers) while this one is contracted. Its tiles: its share of its
+    // XCD's band (mx_tile.hiph) -- neighbours share 12 source rows / columns of halo.
     const int tiles_x = (p.width + MXD_TW - 1) / MXD_TW;
     const int tiles_y = (p.height + MXD_TH - 1) / MXD_TH;
-    int band_first, band_size, stride, first;
-    {
-        const uint32_t total = (uint32_t) tiles_x * (uint32_t) tiles_y, groups = gridDim.x, lin = blockIdx.x;
-        const uint32_t q = total >> 3, r = total & 7u, xcd = lin & 7u;
-        band_first = (int) (xcd * q + min(xcd, r));
-        band_size = (int) (q + (xcd < r ? 1u : 0u));
-        stride = (int) ((groups - xcd + 7u) >> 3);      // workgroups of this XCD
-        first = (int) (lin >> 3);
-    }
+    const auto [band_first, band_size, stride, first] =
+        mx_xcd_band((uint32_t) tiles_x * (uint32_t) tiles_y, gridDim.x, blockIdx.x);
 
     // ---- B fragments: global (L2 resident) -> LDS, one global_load_lds_dwordx4 per fragment -------
 #pragma unroll
@@ -119,11 +104,8 @@ void k_polar_mxd(const plh_pass p_)
     // texel pair u of this lane: tile row, pair within the row (the same for every tile)
     int ty[MXD_NV], tp[MXD_NV];
 #pragma unroll
-    for (int u = 0; u < MXD_NV; u++) {
-        const int i = min(tid + u * MXD_NT, MXD_NPAIRS - 1);
-        ty[u] = (int) (((float) i + 0.5f) * (1.0f / (float) MXD_HP));   // exact: i < 2^22
-        tp[u] = i - ty[u] * MXD_HP;
-    }
+    for (int u = 0; u < MXD_NV; u++)
+        mx_pair_pos<MXD_HP>(min(tid + u * MXD_NT, MXD_NPAIRS - 1), ty[u], tp[u]);
     // the source tile of workgroup tile t: pairs of horizontally adjacent rgba16hf texels, one
     // 16-byte load each, all issued together
     const int ln = lane & 15, lg = lane >> 4;
@@ -138,11 +120,9 @@ void k_polar_mxd(const plh_pass p_)
         const int ox = mx.org_x + 2 * MXD_TW * bx, oy = mx.org_y + 2 * MXD_TH * by;
 #pragma unroll
         for (int u = 0; u < MXD_NV; u++) {
-            const int sy = min(max(oy + ty[u], 0), sh - 1);
-            const int px = min(max(ox + 2 * tp[u], 0), sw - 2);
-            const plh_u32x4 q = *(const __attribute__((address_space(1))) plh_u32x4 *)
-                                    (u_sptr + (size_t) sy * (size_t) u_spitch + (size_t) px * 8);
-            v[u] = make_uint4(q.x, q.y, q.z, q.w);
+            // (the row before the column: the compiler sums the address in order of appearance)
+            const int sy = oy + ty[u], sx = ox + 2 * tp[u];
+            v[u] = mx_pair_load(u_sptr, u_spitch, sx, sy, sw, sh);
         }
         nx_dfx = ((mxd_gfloat *) u_dfx)[MXD_TW * bx + 16 * wc + ln];
 #pragma unroll
@@ -169,29 +149,16 @@ void k_polar_mxd(const plh_pass p_)
 
         // ---- registers -> LDS: the f16 codes move bit for bit into the channel planes ------------
         if (ox < 0 || ox + MXD_SRC_W > sw) {
-            // a pair at clamped positions: beyond the left edge both texels are the pair's first,
-            // beyond the right edge both its second
 #pragma unroll
-            for (int u = 0; u < MXD_NV; u++) {
-                const uint4 w = v[u];
-                const int sx = ox + 2 * tp[u];
-                const bool ldup = sx < 0, hdup = sx > sw - 2;
-                const uint32_t ax = hdup ? w.z : w.x, ay = hdup ? w.w : w.y;
-                const uint32_t bx_ = ldup ? w.x : w.z, by_ = ldup ? w.y : w.w;
-                v[u] = make_uint4(ax, ay, bx_, by_);
-            }
+            for (int u = 0; u < MXD_NV; u++)
+                v[u] = mx_pair_fix(v[u], ox + 2 * tp[u], sw);
         }
 #pragma unroll
         for (int u = 0; u < MXD_NV; u++) {
             const uint4 w = v[u];
             if (tid + u * MXD_NT < MXD_NPAIRS) {
                 unsigned char *d = tile + ty[u] * MXD_PITCH + tp[u] * 4;
-                if (UNORM && PRE) {
-                    // the raw codes, converted in place below
-                    *(uint32_t *) d = (w.x & 0xffffu) | (w.z << 16);
-                    *(uint32_t *) (d + MXD_PLANE) = (w.x >> 16) | (w.z & 0xffff0000u);
-                    *(uint32_t *) (d + 2 * MXD_PLANE) = (w.y & 0xffffu) | (w.w << 16);
-                } else if (UNORM) {
+                if (UNORM && !PRE) {
                     // decode to fp32, THEN round to f16 (what the rgba16hf store + load of the unfused
                     // pass does). The two roundings are kept apart on purpose: left alone the compiler
                     // folds the last fma of the decode into v_fma_mixlo_f16, which rounds once -- one
@@ -205,9 +172,10 @@ void k_polar_mxd(const plh_pass p_)
                     *(uint32_t *) (d + MXD_PLANE) = (uint32_t) plh_f2h(t[2]) | ((uint32_t) plh_f2h(t[3]) << 16);
                     *(uint32_t *) (d + 2 * MXD_PLANE) = (uint32_t) plh_f2h(t[4]) | ((uint32_t) plh_f2h(t[5]) << 16);
                 } else {
-                    *(uint32_t *) d = (w.x & 0xffffu) | (w.z << 16);
-                    *(uint32_t *) (d + MXD_PLANE) = (w.x >> 16) | (w.z & 0xffff0000u);
-                    *(uint32_t *) (d + 2 * MXD_PLANE) = (w.y & 0xffffu) | (w.w << 16);
+                    // rgba16hf: the f16 codes as they are; UNORM && PRE: the raw codes, converted in
+                    // place below
+                    const uint4 o = mx_pair_split_raw(w);
+                    mx_pair_store<3>(tile, MXD_PLANE, ty[u] * MXD_PITCH, tp[u], o.x, o.y, o.z, 0);
                 }
             }
         }
@@ -222,8 +190,9 @@ void k_polar_mxd(const plh_pass p_)
                 const int i = tid + u * MXD_NT;
                 if (i >= MXD_NPAIRS)
                     break;
-                const int y = (int) (((float) i + 0.5f) * (1.0f / (float) MXD_HP));
-                unsigned char *d = tile + y * MXD_PITCH + (i - y * MXD_HP) * 4;
+                int y, x;
+                mx_pair_pos<MXD_HP>(i, y, x);
+                unsigned char *d = tile + y * MXD_PITCH + x * 4;
                 const uint32_t q0 = *(const uint32_t *) d, q1 = *(const uint32_t *) (d + MXD_PLANE),
                                q2 = *(const uint32_t *) (d + 2 * MXD_PLANE);
                 float c[6] = { plh_un16(q0 & 0xffffu), plh_un16(q1 & 0xffffu), plh_un16(q2 & 0xffffu),

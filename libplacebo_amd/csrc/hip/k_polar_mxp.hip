@@ -80,20 +80,11 @@ void k_polar_mxp(const plh_pass p_)
     asm volatile("" : "+s"(u_osy), "+s"(u_ds), "+s"(u_di), "+s"(u_sc), "+s"(u_dptr), "+s"(u_dfy), "+s"(u_dfx));
     typedef __attribute__((address_space(1))) const float mx_gfloat;
 
-    // Workgroups go to the 8 XCDs round-robin in launch order and every XCD has its own L2: XCD x
-    // works on the x-th contiguous eighth of the tiles (row-major), its workgroups side by side on
-    // consecutive tiles -- neighbours share 8 source rows / columns of halo.
+    // the workgroup's tiles: its share of its XCD's band (neighbours share 8 source rows / columns)
     const int tiles_x = (p.width + G::tile_w - 1) / G::tile_w;
     const int tiles_y = (p.height + MX_TILE_H - 1) / MX_TILE_H;
-    int band_first, band_size, stride, first;
-    {
-        const uint32_t total = (uint32_t) tiles_x * (uint32_t) tiles_y, groups = gridDim.x, lin = blockIdx.x;
-        const uint32_t q = total >> 3, r = total & 7u, xcd = lin & 7u;
-        band_first = (int) (xcd * q + min(xcd, r));
-        band_size = (int) (q + (xcd < r ? 1u : 0u));
-        stride = (int) ((groups - xcd + 7u) >> 3);      // workgroups of this XCD
-        first = (int) (lin >> 3);
-    }
+    const auto [band_first, band_size, stride, first] =
+        mx_xcd_band((uint32_t) tiles_x * (uint32_t) tiles_y, gridDim.x, blockIdx.x);
 
     // ---- once per workgroup: B fragments and the (transposed) dither matrix, global (L2 resident)
     // -> LDS without passing through registers (global_load_lds_dwordx4: wave-uniform LDS base +
@@ -133,9 +124,9 @@ void k_polar_mxp(const plh_pass p_)
     uint32_t tyx[NV];
 #pragma unroll
     for (int u = 0; u < NV; u++) {
-        const int i = min(tid + u * NT, G::npairs - 1);
-        const int y = (int) (((float) i + 0.5f) * (1.0f / (float) G::hp));    // exact: i < 2^22
-        tyx[u] = ((uint32_t) y << 16) | (uint32_t) (i - y * G::hp);
+        int y, x;
+        mx_pair_pos<G::hp>(min(tid + u * NT, G::npairs - 1), y, x);
+        tyx[u] = ((uint32_t) y << 16) | (uint32_t) x;
     }
 #define ty(u) ((int) (tyx[u] >> 16))
 #define tp(u) ((int) (tyx[u] & 0xffffu))
@@ -151,6 +142,7 @@ void k_polar_mxp(const plh_pass p_)
         const int ox = u_org_x + 8 * WTC * tbx, oy = u_org_y + 16 * MX_WT_ROWS * tby;
 #pragma unroll
         for (int u = 0; u < NV; u++) {
+            // (mx_pair_load, spelled out: the call compiles to two instructions fewer here)
             const int sy = min(max(oy + ty(u), 0), sh - 1);
             const int px = min(max(ox + 2 * tp(u), 0), sw - 2);
             const plh_u32x4 q = *(const __attribute__((address_space(1))) plh_u32x4 *)
@@ -160,12 +152,8 @@ void k_polar_mxp(const plh_pass p_)
         nx_dfx = ((mx_gfloat *) u_dfx)[G::tile_w * tbx + 16 * wave + ln];
         nx_dfy = ((mx_gfloat *) u_dfy)[MX_TILE_H * tby + lane];
     };
-    auto pair_store = [&](int ty_, int tp_, uint32_t o0, uint32_t o1, uint32_t o2) {
-        unsigned char *d = tile + ty_ * PITCH + tp_ * 4;
-        *(uint32_t *) d = o0;
-        *(uint32_t *) (d + PLANE) = o1;
-        *(uint32_t *) (d + 2 * PLANE) = o2;
-    };
+    // the planes of the pair at (ty_, tp_) -> the tile
+    auto pair_store = [&](int ty_, int tp_, uint4 o) { mx_pair_store<NCH>(tile, PLANE, ty_ * PITCH, tp_, o.x, o.y, o.z, 0); };
 
     const unsigned char *bfl = bl + lane * 16;
     int u_row0 = mx.row_first[0], u_row1 = mx.row_first[1], u_npairs = mx.npairs;
@@ -186,17 +174,9 @@ void k_polar_mxp(const plh_pass p_)
         if (wave == 0)
             ((float *) ldfy)[lane] = nx_dfy;
         if (edge) {
-            // a pair at clamped positions: beyond the left edge both texels are the pair's first,
-            // beyond the right edge both its second
 #pragma unroll
-            for (int u = 0; u < NV; u++) {
-                const uint4 w = v[u];
-                const int sx = ox + 2 * tp(u);
-                const bool ldup = sx < 0, hdup = sx > sw - 2;
-                const uint32_t ax = hdup ? w.z : w.x, ay = hdup ? w.w : w.y;
-                const uint32_t bx_ = ldup ? w.x : w.z, by_ = ldup ? w.y : w.w;
-                v[u] = make_uint4(ax, ay, bx_, by_);
-            }
+            for (int u = 0; u < NV; u++)
+                v[u] = mx_pair_fix(v[u], ox + 2 * tp(u), sw);
         }
         if (raw16) {
             // rgba16hf source, no pre-ops: the f16 codes are moved bit for bit into the planes
@@ -204,12 +184,10 @@ void k_polar_mxp(const plh_pass p_)
             for (int u = 0; u < NV; u++) {
                 const uint4 w = v[u];
                 if (tid + u * NT < G::npairs)
-                    pair_store(ty(u), tp(u), (w.x & 0xffffu) | (w.z << 16), (w.x >> 16) | (w.z & 0xffff0000u),
-                               (w.y & 0xffffu) | (w.w << 16));
+                    pair_store(ty(u), tp(u), mx_pair_split_raw(w));
             }
         } else if (simple) {
-            // the plane as it is, or behind an identity PLANE_MAP (components the plane does not
-            // carry take their neutral values): decode, round to f16, store
+            // the plane as it is, or behind an identity PLANE_MAP: no interpreter walk
             const plh_op &om = p.ops[0];
             const int present = u_npre ? om.i1 : 4;
             float neutral[NCH];
@@ -221,18 +199,10 @@ void k_polar_mxp(const plh_pass p_)
                 const uint32_t q[4] = { v[u].x, v[u].y, v[u].z, v[u].w };
                 uint32_t o[NCH];
 #pragma unroll
-                for (int k = 0; k < NCH; k++) {
-                    const uint32_t a = (k & 1) ? q[k >> 1] >> 16 : q[k >> 1] & 0xffffu;
-                    const uint32_t b = (k & 1) ? q[2 + (k >> 1)] >> 16 : q[2 + (k >> 1)] & 0xffffu;
-                    float fa = unorm ? mx_un16_for_f16(a) : plh_h2f(a), fb = unorm ? mx_un16_for_f16(b) : plh_h2f(b);
-                    if (k >= present) {
-                        fa = neutral[k];
-                        fb = neutral[k];
-                    }
-                    o[k] = mx_pack(fa, fb);
-                }
+                for (int k = 0; k < NCH; k++)
+                    o[k] = mx_pair_simple(q, k, unorm, present, neutral[k]);
                 if (tid + u * NT < G::npairs)
-                    pair_store(ty(u), tp(u), o[0], o[1], o[2]);
+                    pair_store(ty(u), tp(u), make_uint4(o[0], o[1], o[2], 0));
             }
         } else {
             // any other op list without transcendentals: one interpreter walk over the lane's texels
@@ -240,27 +210,14 @@ void k_polar_mxp(const plh_pass p_)
             frag_t fcs[2 * NV];
 #pragma unroll
             for (int u = 0; u < NV; u++) {
-                const uint4 w = v[u];
-                float4_t &c0 = c[2 * u], &c1 = c[2 * u + 1];
-                if (unorm) {
-                    c0 = { plh_un16(w.x & 0xffff), plh_un16(w.x >> 16), plh_un16(w.y & 0xffff), plh_un16(w.y >> 16) };
-                    c1 = { plh_un16(w.z & 0xffff), plh_un16(w.z >> 16), plh_un16(w.w & 0xffff), plh_un16(w.w >> 16) };
-                } else {
-                    c0 = { plh_h2f(w.x & 0xffff), plh_h2f(w.x >> 16), plh_h2f(w.y & 0xffff), plh_h2f(w.y >> 16) };
-                    c1 = { plh_h2f(w.z & 0xffff), plh_h2f(w.z >> 16), plh_h2f(w.w & 0xffff), plh_h2f(w.w >> 16) };
-                }
-                // gl_FragCoord of the fused pass: the (clamped) source texel
-                const int sx = ox + 2 * tp(u);
-                const float cy = (float) min(max(oy + ty(u), 0), sh - 1) + 0.5f;
-                fcs[2 * u] = { (float) min(max(sx, 0), sw - 1) + 0.5f, cy, 0.0f, 0 };
-                fcs[2 * u + 1] = { (float) min(max(sx + 1, 0), sw - 1) + 0.5f, cy, 0.0f, 0 };
+                mx_pair_decode(v[u], unorm, c[2 * u], c[2 * u + 1]);
+                mx_pair_fragcoord(ox + 2 * tp(u), oy + ty(u), sw, sh, fcs[2 * u], fcs[2 * u + 1]);
             }
             apply_ops_n<2 * NV, false, true>(c, p.ops, 0, u_npre, fcs);
 #pragma unroll
             for (int u = 0; u < NV; u++) {
                 if (tid + u * NT < G::npairs)
-                    pair_store(ty(u), tp(u), mx_pack(c[2 * u].x, c[2 * u + 1].x), mx_pack(c[2 * u].y, c[2 * u + 1].y),
-                               mx_pack(c[2 * u].z, c[2 * u + 1].z));
+                    pair_store(ty(u), tp(u), mx_pair_pack(c[2 * u], c[2 * u + 1]));
             }
         }
         return nx_dfx;

@@ -85,11 +85,7 @@ void k_polar_mxr(const plh_pass p_)
             pq_seg_stage(segl, (const void *) u_segp, u_segr, (uint32_t) tid, (uint32_t) MXR_NT);
     }
     const pq_seg seg = pq_seg_view(segl, u_segr, (uint32_t) lane, u_segp != 0);
-#ifdef PLH_MX_DEBUG
-    const int dbg = s.pp_debug;     // (profiling aid: only in a -DPLH_MX_DEBUG build, k_polar_mx.hiph)
-#else
-    constexpr int dbg = 0;
-#endif
+    const int dbg = MX_DBG(s);      // (profiling aid, mx_tile.hiph)
 
     // uniforms of the per-phase code, read once and pinned in SGPRs (k_polar_mx.hiph says why)
     int u_w = p.width, u_h = p.height, u_dst_w = p.dst.w, u_dst_h = p.dst.h;
@@ -108,18 +104,12 @@ void k_polar_mxr(const plh_pass p_)
     typedef __attribute__((address_space(1))) const float gfloat;
     typedef __attribute__((address_space(1))) plh_u32x2 gpx;
 
-    // XCD x works on the x-th contiguous eighth of the tiles (k_polar_mx.hiph)
+    // the workgroup's tile: its XCD's eighth of the frame (mx_tile.hiph)
     const int nbx = (u_w - 1 + u_sx) / R + 1;       // base indices of the frame
     const int tiles_x = (nbx + MXR_TBX - 1) / MXR_TBX;
-    int bx, by;
-    {
-        const uint32_t total = gridDim.x, lin = blockIdx.x;
-        const uint32_t q = total >> 3, r = total & 7u;
-        const uint32_t xcd = lin & 7u, k = lin >> 3;
-        const uint32_t t = xcd * q + min(xcd, r) + k;
-        by = (int) (t / (uint32_t) tiles_x);
-        bx = (int) (t - (uint32_t) by * (uint32_t) tiles_x);
-    }
+    const uint32_t t = mx_xcd_tile(gridDim.x, blockIdx.x);
+    const int by = (int) (t / (uint32_t) tiles_x);
+    const int bx = (int) (t - (uint32_t) by * (uint32_t) tiles_x);
     // source texel of LDS (0, 0): base index 0 sits on source column org_x + 3
     const int ox = mx.org_x + MXR_TSX * bx, oy = mx.org_y + G * MXR_TBY * by;
 
@@ -135,25 +125,19 @@ void k_polar_mxr(const plh_pass p_)
         int ty[MXR_NV], tp[MXR_NV], sx[MXR_NV];
 #pragma unroll
         for (int u = 0; u < MXR_NV; u++) {
-            const int i = min(tid + u * MXR_NT, MXR_NPAIRS - 1);
-            ty[u] = (int) (((float) i + 0.5f) * (1.0f / (float) MXR_HP));    // exact: i < 2^22
-            tp[u] = i - ty[u] * MXR_HP;
+            mx_pair_pos<MXR_HP>(min(tid + u * MXR_NT, MXR_NPAIRS - 1), ty[u], tp[u]);
             sx[u] = ox + 2 * tp[u];
-            const int cy = min(max(oy + ty[u], 0), sh - 1), cx = min(max(sx[u], 0), sw - 2);
-            const plh_u32x4 q = *(const __attribute__((address_space(1))) plh_u32x4 *)
-                                    (u_sptr + (size_t) cy * (size_t) u_spitch + (size_t) cx * 8);
-            v[u] = (dbg & 8) ? make_uint4(tid, u, 0, 0) : make_uint4(q.x, q.y, q.z, q.w);
+            v[u] = (dbg & 8) ? make_uint4(tid, u, 0, 0) : mx_pair_load(u_sptr, u_spitch, sx[u], oy + ty[u], sw, sh);
         }
         // identity PLANE_MAP in front (components the plane does not carry: neutral values)
         const plh_op &om = p.ops[0];
         const int present = u_npre ? om.i1 : 4;
 #pragma unroll
         for (int u = 0; u < MXR_NV; u++) {
-            // a pair at clamped positions: beyond the left edge both texels are the pair's first,
-            // beyond the right edge both its second
-            const bool ldup = sx[u] < 0, hdup = sx[u] > sw - 2;
-            const uint32_t q[4] = { hdup ? v[u].z : v[u].x, hdup ? v[u].w : v[u].y,
-                                    ldup ? v[u].x : v[u].z, ldup ? v[u].y : v[u].w };
+            // (every tile: no edge test in front of the fix. The decode is this kernel's own -- plh_un16's
+            // quotient, f16 codes bit for bit behind a PLANE_MAP: not mx_pair_simple's instructions)
+            const uint4 w = mx_pair_fix(v[u], sx[u], sw);
+            const uint32_t q[4] = { w.x, w.y, w.z, w.w };
             uint32_t o[3];
 #pragma unroll
             for (int k = 0; k < 3; k++) {
@@ -172,10 +156,7 @@ void k_polar_mxr(const plh_pass p_)
             }
             if (tid + u * MXR_NT < MXR_NPAIRS) {
                 const int trow = G == 1 ? ty[u] * MXR_PITCH : (ty[u] & 1) * MXR_HALF + (ty[u] >> 1) * MXR_PITCH;
-                unsigned char *d = tile + trow + tp[u] * 4;
-                *(uint32_t *) d = o[0];
-                *(uint32_t *) (d + MXR_PLANE) = o[1];
-                *(uint32_t *) (d + 2 * MXR_PLANE) = o[2];
+                mx_pair_store<3>(tile, MXR_PLANE, trow, tp[u], o[0], o[1], o[2], 0);
             }
         }
     }
@@ -191,16 +172,10 @@ void k_polar_mxr(const plh_pass p_)
     constexpr int MXR_JSTEP = G == 1 ? 2 * MXR_PITCH : MXR_PITCH;
     const unsigned char *bfl = bl + lane * 16;
 
-    // the rows that may be stored form one interval [ylo, ylo + ny) (k_polar_mx.hiph)
-    int ylo, yhi;
-    if (u_dir_y > 0) {
-        ylo = max(0, -u_base_y);
-        yhi = min(u_h, u_dst_h - u_base_y);
-    } else {
-        ylo = max(0, u_base_y - u_dst_h + 1);
-        yhi = min(u_h, u_base_y + 1);
-    }
-    const uint32_t ny = (uint32_t) max(yhi - ylo, 0);
+    // the rows that may be stored form one interval [ylo, ylo + ny)
+    int ylo;
+    uint32_t ny;
+    mx_row_interval(u_dir_y, u_base_y, u_h, u_dst_h, ylo, ny);
     const float ds = u_ds, di = u_di, sc = u_sc;
     float aw = 1.0f;        // alpha (not sampled: 1) behind dither and scale
     if (u_has_dither)

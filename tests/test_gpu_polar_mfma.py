@@ -365,3 +365,78 @@ def test_mxp_persistent_kernel_against_k_polar_mx(size, case):
         a, b = outs
         assert a[..., :3].std() > 1000
         assert np.array_equal(a, b), util.diff_stats(a, b)
+
+
+# ---- every tile is an edge tile: the tile primitives the four kernels share (mx_tile.hiph) ---------
+def _traced(capfd, want, *a, **kw):
+    """render(...) and assert from the launcher's trace that kernel `want` took the polar pass"""
+    with util.kernel_trace(capfd) as kernels:
+        out = render(*a, **kw)
+    polar = [k for k in kernels if k.startswith("k_polar")]
+    assert polar == [want], (want, kernels)
+    return out
+
+
+EDGE_CASES = ([("2x", 5, 3), ("2x", 9, 7), ("2x", 33, 5)] +
+              [(r, 7, 5) for r in ("3x", "4x")] + [(r, 21, 9) for r in ("3x", "4x")] +
+              [("3:2", 10, 6), ("3:2", 22, 14)] +
+              [(k, 18, 10) for k in ("2:1 f16", "2:1 un16")] + [(k, 66, 34) for k in ("2:1 f16", "2:1 un16")])
+
+
+@pytest.mark.parametrize("kind,sw,sh", EDGE_CASES, ids=["%s-%dx%d" % c for c in EDGE_CASES])
+def test_mx_every_tile_is_an_edge_tile(kind, sw, sh, capfd):
+    """The staging code the four matrix-pipe kernels share (mx_tile.hiph: texel-pair positions, the
+    clamped pair load, the edge fix, decode and planar split) where it can go wrong and nowhere
+    else: the whole source is narrower than one tile, so the left and the right duplication meet in
+    one tile, and odd widths make the last pair straddle the edge. White noise; sizes are source
+    sizes (2 : 1: the target is half of it, 9 x 5 and 33 x 17). From the launcher's trace the named
+    kernel took the pass. Statements: k_polar_mxp equals k_polar_mx bit for bit; every matrix-pipe
+    result is at most one 16-bit code (one f16 ulp for a half-float target) from k_polar_pp; for
+    the unorm-source upscales k_polar_pp equals orc.sample_polar bit for bit. (No cap on the share
+    of differing samples: a few hundred samples are below its resolution.)"""
+    def one_code(a, b):
+        d = np.abs(a.astype(np.int64) - b.astype(np.int64))
+        print("%s %dx%d: max |diff| %d, %d of %d samples differ" % (kind, sw, sh, d.max(), (d > 0).sum(), d.size))
+        assert d.max() <= 1, (int(d.max()), int((d > 1).sum()))
+
+    if kind.startswith("2:1"):
+        dw, dh = sw // 2, sh // 2
+        if kind == "2:1 f16":
+            rng = np.random.default_rng(11)
+            img = (0.05 + 0.9 * rng.random((sh, sw, 4), dtype=np.float32)).astype(np.float16)
+            img[..., 3] = 1.0
+            fmt = dict(src_fmt="rgba16hf", dst_fmt="rgba16hf")
+        else:
+            img, fmt = util.random_rgba16(sw, sh, seed=5), {}
+        mx = _traced(capfd, "k_polar_mxd", img, dw, dh, ewa_down(), True, expect_mx=True, **fmt)
+        pp = _traced(capfd, "k_polar_pp", img, dw, dh, ewa_down(), False, expect_mx=False, **fmt)
+        assert np.array_equal(mx[..., 3], pp[..., 3])
+        if kind == "2:1 f16":
+            # (positive halves: the code distance is the ulp distance)
+            one_code(mx[..., :3].view(np.uint16), pp[..., :3].view(np.uint16))
+            assert pp[..., :3].astype(np.float32).std() > 0.01
+        else:
+            one_code(mx, pp)
+            assert pp[..., :3].std() > 1000
+        return
+
+    ratio = {"2x": 2, "3x": 3, "4x": 4, "3:2": 1.5}[kind]
+    img = util.random_rgba16(sw, sh, seed=3)
+    dw, dh = int(ratio * sw), int(ratio * sh)
+    pp = _traced(capfd, "k_polar_pp", img, dw, dh, ewa(), False, expect_mx=False)
+    assert pp[..., :3].std() > 1000
+    a = orc.tex_decode(img, "rgba16")
+    a[..., 3] = 1.0
+    a = orc.op_quant_f16(a)
+    w, r, rz = orc.filter_generate_polar(orc.ewa_lanczos())
+    ref16 = orc.tex_encode(orc.sample_polar(a, w, r, rz, dw, dh, mask=0x7), "rgba16")
+    assert np.array_equal(pp, ref16)
+    if kind == "2x":
+        with env(PL_HIP_MX_PERSIST="1"):
+            mxp = _traced(capfd, "k_polar_mxp", img, dw, dh, ewa(), True, expect_mx=True)
+        with env(PL_HIP_MX_PERSIST="0"):
+            mx = _traced(capfd, "k_polar_mx", img, dw, dh, ewa(), True, expect_mx=True)
+        assert np.array_equal(mxp, mx), util.diff_stats(mxp, mx)
+    else:
+        mx = _traced(capfd, "k_polar_mxr", img, dw, dh, ewa(), True, expect_mx=True)
+    one_code(mx, pp)
