@@ -33,9 +33,6 @@ int plh_dev_open(int device, struct plh_dev_info *info);
 int plh_stream_create(int device, plh_stream *out);
 // the device that owns `s` (not the calling thread's current one) and, optionally, its CU count
 int plh_stream_device(plh_stream s, int *cus);
-// raise a kernel's dynamic-LDS limit on the stream's device, once per (kernel, device); `done` =
-// the caller's static per-kernel device mask
-int plh_kernel_needs_lds(const void *kernel, plh_stream s, size_t bytes, uint64_t *done);
 // the PQ transfer pair as piecewise cubics (pqseg.hiph) on the device that owns `s`: built and
 // uploaded on first use; consts = { m1, c3, m2, 1 / m2, 1 / m1 }. NULL = not available
 const void *plh_pqseg_tables(plh_stream s, const float consts[5]);

@@ -87,24 +87,35 @@ int plh_stream_device(plh_stream s, int *cus)
     return dev;
 }
 
-// Raise `kernel`'s dynamic-LDS limit to `bytes` on the device that owns `s`; `done` is the
-// caller's per-kernel bit mask of devices already served (a static uint64_t next to the launch).
-int plh_kernel_needs_lds(const void *kernel, plh_stream s, size_t bytes, uint64_t *done)
+// Raise `kernel`'s dynamic-LDS limit on the device that owns `s` to the largest request so far (a device
+// served later must not be left with a smaller limit); `st`: the kernel's state (devmath.hiph). A larger
+// request clears the mask of served devices BEFORE it publishes its size and a reader takes the size
+// first, so a mask seen next to a size belongs to that size or to a larger one.
+static std::mutex g_lds_mutex;
+
+int plh_kernel_needs_lds(const void *kernel, plh_stream s, size_t bytes, struct plh_lds_limit *st)
 {
     const int dev = plh_stream_device(s, NULL);
     const uint64_t bit = 1ull << dev;
-    if (__atomic_load_n(done, __ATOMIC_ACQUIRE) & bit)
+    if (bytes <= __atomic_load_n(&st->bytes, __ATOMIC_ACQUIRE) && (__atomic_load_n(&st->done, __ATOMIC_ACQUIRE) & bit))
+        return 0;
+    std::lock_guard<std::mutex> lock(g_lds_mutex);
+    if (bytes > st->bytes) {
+        __atomic_store_n(&st->done, 0, __ATOMIC_RELEASE);
+        __atomic_store_n(&st->bytes, bytes, __ATOMIC_RELEASE);
+    }
+    if (st->done & bit)
         return 0;
     int cur = dev;
     (void) hipGetDevice(&cur);
     if (cur != dev && hipSetDevice(dev) != hipSuccess)
         return -(int) hipErrorInvalidDevice;
-    const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
+    const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) st->bytes);
     if (cur != dev)
         (void) hipSetDevice(cur);
     if (err != hipSuccess)
         return -(int) err;
-    __atomic_fetch_or(done, bit, __ATOMIC_RELEASE);
+    __atomic_fetch_or(&st->done, bit, __ATOMIC_RELEASE);
     return 0;
 }
 

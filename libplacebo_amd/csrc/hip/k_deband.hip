@@ -600,21 +600,15 @@ int plh_launch_deband(hipStream_t stream, const plh_pass *pass)
             // (8 bands of tile columns, padded to the widest: k_deband_lds)
 #define DBL_LAUNCH(TH) do { \
                 const size_t shmem = (size_t) DBL_WW * (TH + 2 * DBL_HALO) * 8; \
-                static uint64_t lds_done; \
-                const int e = plh_kernel_needs_lds((const void *) k_deband_lds<TH>, (plh_stream) stream, shmem, &lds_done); \
-                if (e) \
-                    return e; \
                 const int tiles_y = (pass->height + TH - 1) / TH; \
                 const dim3 grid(8 * ((tiles_x + 7) / 8) * tiles_y); \
-                PLH_LAUNCH_LAST(k_deband_lds<TH>, grid, dim3(DBL_NT), shmem, stream, *pass); \
+                return plh_launch_last_lds<k_deband_lds<TH>>(grid, dim3(DBL_NT), shmem, stream, *pass); \
             } while (0)
             // fewer than two rounds of 32-row tiles (three workgroups per CU): 16-row tiles
             if (tiles_x * ((pass->height + 31) / 32) < 2 * 3 * cus)
                 DBL_LAUNCH(16);
-            else
-                DBL_LAUNCH(32);
+            DBL_LAUNCH(32);
 #undef DBL_LAUNCH
-            return plh_launch_status();
         }
         const int nbx = (pass->width + 2 * DBF_BW - 1) / (2 * DBF_BW);
         const int nby = (pass->height + DBF_BH - 1) / DBF_BH;

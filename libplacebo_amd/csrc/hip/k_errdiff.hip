@@ -101,10 +101,8 @@ extern "C" int plh_launch_errdiff(plh_stream stream, const plh_errdiff_args *arg
     const size_t shmem = (size_t) args->ring_rows * args->ring_cols * sizeof(uint32_t);
     if (shmem > 160 * 1024)
         return -1000;
-    // opt in to more than the default 64 KiB of dynamic LDS, once per device
-    static uint64_t lds_done;
-    if (shmem > 64 * 1024)
-        (void) plh_kernel_needs_lds((const void *) k_errdiff, stream, 160 * 1024, &lds_done);
+    if (const int e = plh_launch_needs_lds<k_errdiff>((hipStream_t) stream, shmem))
+        return e;
     hipLaunchKernelGGL(k_errdiff, dim3(1), dim3(args->block_size), shmem, (hipStream_t) stream,
                        *args);
     return plh_launch_status();

@@ -262,27 +262,6 @@ __global__ void k_polar_weights(const plh_pass p_, const float *clsx, int ncx,
     w[s.num_taps] = s.scale / wsum;     // color = scale / wsum * color, sampling.c:897
 }
 
-// Uniform read-only tables are read through the constant address space so that
-// they become s_load_* (SGPR) instead of per-lane flat loads in the tap loop.
-// k_polar_pp_f16.hip / k_polar_pp_f32.hip
-int plh_launch_polar_pp_f16(hipStream_t stream, const plh_pass *pass, dim3 grid, dim3 block,
-                            size_t shmem, int n);
-int plh_launch_polar_pp_f32(hipStream_t stream, const plh_pass *pass, dim3 grid, dim3 block,
-                            size_t shmem, int n);
-int plh_launch_polar_pp_f16_c12(hipStream_t stream, const plh_pass *pass, dim3 grid, dim3 block,
-                                size_t shmem, int n);
-int plh_launch_polar_pp_f32_c12(hipStream_t stream, const plh_pass *pass, dim3 grid, dim3 block,
-                                size_t shmem, int n);
-// k_polar_mx.hip
-int plh_launch_polar_mx(hipStream_t stream, const plh_pass *pass);
-// k_polar_mxp.hip: the same on persistent workgroups, for the commonest shapes
-bool plh_polar_mxp_applies(const plh_pass *pass);
-int plh_launch_polar_mxp(hipStream_t stream, const plh_pass *pass);
-bool plh_polar_mxd_applies(plh_pass *pass);
-int plh_launch_polar_mxd(hipStream_t stream, const plh_pass *pass);
-bool plh_polar_mxr_applies(plh_pass *pass);
-int plh_launch_polar_mxr(hipStream_t stream, const plh_pass *pass);
-
 int plh_launch_polar_classify(plh_stream stream, const plh_pass *pass, void *out)
 {
     const int n = pass->width > pass->height ? pass->width : pass->height;
@@ -299,88 +278,91 @@ int plh_launch_polar_weights(plh_stream stream, const plh_pass *pass, const floa
     return plh_launch_status();
 }
 
-template <typename T, uint32_t MASK>
-static int launch_ar(hipStream_t stream, const plh_pass *pass, dim3 grid, dim3 block, size_t shmem)
+// The two candidates that live here (polar_common.hiph: the contract).
+// k_polar_pp: a geometry with phase-class tables; RGB / RGBA tiles or one- and two-component planes
+static bool plh_polar_pp_applies(plh_pass *pass)
 {
-    if (pass->s.antiring > 0.0f)
-        PLH_LAUNCH_LAST((k_polar<T, MASK, true>), grid, block, shmem, stream, *pass);
-    else
-        PLH_LAUNCH_LAST((k_polar<T, MASK, false>), grid, block, shmem, stream, *pass);
-    return plh_launch_status();
-}
-
-template <typename T>
-static int launch_mask(hipStream_t stream, const plh_pass *pass, dim3 grid, dim3 block, size_t shmem)
-{
-    switch (pass->s.comp_mask & 0xf) {
-    case 0x1: return launch_ar<T, 0x1>(stream, pass, grid, block, shmem);
-    case 0x3: return launch_ar<T, 0x3>(stream, pass, grid, block, shmem);
-    case 0x7: return launch_ar<T, 0x7>(stream, pass, grid, block, shmem);
-    default:  return launch_ar<T, 0xf>(stream, pass, grid, block, shmem);
-    }
-}
-
-int plh_launch_polar(hipStream_t stream, const plh_pass *pass_in)
-{
-    plh_pass local = *pass_in;
-    const plh_pass *pass = &local;
-    const dim3 block(POLAR_BW, POLAR_BH);
     const uint32_t cm = pass->s.comp_mask & 0xf;
-    if (pass->s.pp && plh_polar_mxd_applies(&local)) {
-        plh_trace_kernel("k_polar_mxd");
-        return plh_launch_polar_mxd(stream, pass);     // the 2 : 1 downscale on the matrix pipe
-    }
-    if (pass->s.pp && pass->s.mx.enabled == 3) {
-        // an integer upscale by 3 or 4 on the matrix pipe, where the pass has the kernel's shape
-        plh_pass probe = local;
-        if (plh_polar_mxr_applies(&probe)) {
-            plh_trace_kernel("k_polar_mxr");
-            return plh_launch_polar_mxr(stream, &probe);
-        }
-    }
-    if (pass->s.pp && pass->s.mx.enabled == 1 && (cm == 0x7 || cm == 0xf)) {
-        // (the matrix-pipe kernel has a variant for the map chain of an HDR pass)
-        if (cm == 0x7)
-            plh_match_map_chain(&local, true);
-        if (!local.chain.enabled)
-            plh_match_fast_epilogue(&local);
-        if (plh_polar_mxp_applies(pass)) {
-            plh_trace_kernel("k_polar_mxp");
-            return plh_launch_polar_mxp(stream, pass);
-        }
-        plh_trace_kernel("k_polar_mx");
-        return plh_launch_polar_mx(stream, pass);
-    }
-    // the phase-class kernels have a CHAIN variant for RGB / RGBA tiles (k_polar_pp.hiph)
-    if (pass->s.pp && (cm == 0x7 || cm == 0xf))
-        plh_match_map_chain(&local);
-    if (!local.chain.enabled)
-        plh_match_fast_epilogue(&local);
-    if (pass->s.pp && (cm == 0x7 || cm == 0xf || cm == 0x1 || cm == 0x3)) {
-        const int n = pass->s.pp_n, cw = pass->s.pp_cells_w, ch = pass->s.pp_cells_h;
-        const int cth = POLAR_BH * pass->s.tile_rows;
-        const dim3 grid((cw + POLAR_BW - 1) / POLAR_BW, (ch + cth - 1) / cth);
-        const size_t px = pass->s.tile_fp32 ? sizeof(float4) : sizeof(uint2);
-        const size_t shmem = PP_LDS_FIXED + pass->s.pp_lds_weights +
-                             (size_t) pass->s.tile_w * pass->s.tile_h * px;
-        if (shmem > 160 * 1024)
-            return -1000;
-        const bool planes = cm == 0x1 || cm == 0x3;
-        plh_trace_kernel("k_polar_pp");
-        if (pass->s.tile_fp32)
-            return planes ? plh_launch_polar_pp_f32_c12(stream, pass, grid, block, shmem, n)
-                          : plh_launch_polar_pp_f32(stream, pass, grid, block, shmem, n);
-        return planes ? plh_launch_polar_pp_f16_c12(stream, pass, grid, block, shmem, n)
-                      : plh_launch_polar_pp_f16(stream, pass, grid, block, shmem, n);
-    }
-    const int th = POLAR_BH * pass->s.tile_rows;
-    const dim3 grid((pass->width + POLAR_BW - 1) / POLAR_BW, (pass->height + th - 1) / th);
-    const size_t px = pass->s.tile_fp32 ? sizeof(float4) : sizeof(uint2);
-    const size_t shmem = 256 * sizeof(float2) + (size_t) pass->s.tile_w * pass->s.tile_h * px;
+    if (!pass->s.pp || (cm != 0x7 && cm != 0xf && cm != 0x1 && cm != 0x3))
+        return false;
+    // (the kernel has a CHAIN variant for RGB / RGBA tiles, k_polar_pp.hiph)
+    if (cm == 0x7 || cm == 0xf)
+        plh_match_map_chain(pass);
+    if (!pass->chain.enabled)
+        plh_match_fast_epilogue(pass);
+    return true;
+}
+
+static int plh_launch_polar_pp(hipStream_t stream, const plh_pass *pass)
+{
+    const plh_sampler_args &s = pass->s;
+    const int cth = POLAR_BH * s.tile_rows;
+    const dim3 grid((s.pp_cells_w + POLAR_BW - 1) / POLAR_BW, (s.pp_cells_h + cth - 1) / cth);
+    const dim3 block(POLAR_BW, POLAR_BH);
+    const size_t px = s.tile_fp32 ? sizeof(float4) : sizeof(uint2);
+    const size_t shmem = PP_LDS_FIXED + s.pp_lds_weights + (size_t) s.tile_w * s.tile_h * px;
+    // (not reached: polar_tables.c sizes the tile and the weights' slice to 64 KiB together -- its
+    // `max_lds` loop -- or builds no tables, and then s.pp is NULL)
     if (shmem > 160 * 1024)
-        return -1000; // host picks tile sizes that fit; see shader_sampling.c, polar_tables.c
-    plh_trace_kernel("k_polar");
-    if (pass->s.tile_fp32)
-        return launch_mask<float>(stream, pass, grid, block, shmem);
-    return launch_mask<__half>(stream, pass, grid, block, shmem);
+        return -1000;
+    const bool planes = (s.comp_mask & 0xf) == 0x1 || (s.comp_mask & 0xf) == 0x3;
+    if (s.tile_fp32)
+        return planes ? plh_launch_polar_pp_f32_c12(stream, pass, grid, block, shmem, s.pp_n)
+                      : plh_launch_polar_pp_f32(stream, pass, grid, block, shmem, s.pp_n);
+    return planes ? plh_launch_polar_pp_f16_c12(stream, pass, grid, block, shmem, s.pp_n)
+                  : plh_launch_polar_pp_f16(stream, pass, grid, block, shmem, s.pp_n);
+}
+
+// k_polar: per-pixel weights, the recorded ops interpreted -- any polar pass
+static bool plh_polar_px_applies(plh_pass *) { return true; }
+
+// k_polar's instance for the tile's texels T, the component mask and anti-ringing
+template <typename T>
+static plh_pass_launch_fn *px_instance(const plh_pass *pass)
+{
+#define PX(MASK) return pass->s.antiring > 0.0f ? plh_launch_last_lds<k_polar<T, MASK, true>> \
+                                                : plh_launch_last_lds<k_polar<T, MASK, false>>
+    switch (pass->s.comp_mask & 0xf) {
+    case 0x1: PX(0x1);
+    case 0x3: PX(0x3);
+    case 0x7: PX(0x7);
+    default:  PX(0xf);
+    }
+#undef PX
+}
+
+static int plh_launch_polar_px(hipStream_t stream, const plh_pass *pass)
+{
+    const plh_sampler_args &s = pass->s;
+    const int th = POLAR_BH * s.tile_rows;
+    const dim3 grid((pass->width + POLAR_BW - 1) / POLAR_BW, (pass->height + th - 1) / th);
+    const size_t px = s.tile_fp32 ? sizeof(float4) : sizeof(uint2);
+    const size_t shmem = 256 * sizeof(float2) + (size_t) s.tile_w * s.tile_h * px;
+    // (not reached: pl_shader_sample_polar, shader_sampling.c, fails a shader whose tile -- this sum --
+    // is above 160 KiB. It does size tiles of steep downscales above 64 KiB: plh_launch_last_lds asks)
+    if (shmem > 160 * 1024)
+        return -1000;
+    plh_pass_launch_fn *launch = s.tile_fp32 ? px_instance<float>(pass) : px_instance<__half>(pass);
+    return launch(grid, dim3(POLAR_BW, POLAR_BH), shmem, stream, *pass);
+}
+
+// The kernels for a polar pass, in the order they are tried; each on a copy of the pass of its own
+int plh_launch_polar(hipStream_t stream, const plh_pass *pass)
+{
+    static const struct { const char *name; plh_polar_applies_fn *applies; plh_polar_launch_fn *launch; } candidates[] = {
+        { "k_polar_mxd", plh_polar_mxd_applies, plh_launch_polar_mxd },   // matrix pipe: the 2 : 1 downscale
+        { "k_polar_mxr", plh_polar_mxr_applies, plh_launch_polar_mxr },   // ... the 3x, 4x, 3 : 2 upscales
+        { "k_polar_mxp", plh_polar_mxp_applies, plh_launch_polar_mxp },   // ... the 2x upscale, persistent, commonest op shapes
+        { "k_polar_mx",  plh_polar_mx_applies,  plh_launch_polar_mx },    // ... the 2x upscale, every op shape
+        { "k_polar_pp",  plh_polar_pp_applies,  plh_launch_polar_pp },    // phase classes: every geometry with tables
+        { "k_polar",     plh_polar_px_applies,  plh_launch_polar_px },    // every pass
+    };
+    for (const auto &c : candidates) {
+        plh_pass local = *pass;
+        if (c.applies(&local)) {
+            plh_trace_kernel(c.name);
+            return c.launch(stream, &local);
+        }
+    }
+    return -(int) hipErrorInvalidValue;     // (not reached: the last candidate takes every pass)
 }

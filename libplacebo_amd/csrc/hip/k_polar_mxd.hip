@@ -351,11 +351,37 @@ void k_polar_mxd(const plh_pass p_)
     }
 }
 
+// The kernel's instance for a pass whose formats and op shape plh_polar_mxd_applies has accepted, or
+// NULL: there is none. Ten of the sixteen exist -- a LINEARIZE pre-op comes with an rgba16 source only,
+// and such a source is delinearised only where it has been linearised (the other order is k_polar_pp's).
+static plh_pass_launch_fn *mxd_instance(const plh_pass *pass)
+{
+    const bool unorm = pass->s.src.fmt == PLH_FMT_RGBA16, f16dst = pass->dst.fmt == PLH_FMT_RGBA16F;
+    const bool pre = pass->num_pre_ops && pass->ops[pass->num_pre_ops - 1].kind == PLH_OP_LINEARIZE;
+    const bool delin = pass->num_pre_ops < pass->num_ops && pass->ops[pass->num_pre_ops].kind == PLH_OP_DELINEARIZE;
+#define MXD(U, F, P, D) return plh_launch_last_lds<k_polar_mxd<U, F, P, D>>
+    if (pre || delin) {
+        // the passes of a linear-light downscale
+        if (unorm && pre && f16dst && !delin)   MXD(true, true, true, false);
+        if (unorm && pre && f16dst)             MXD(true, true, true, true);
+        if (unorm && pre && delin)              MXD(true, false, true, true);
+        if (unorm && pre)                       MXD(true, false, true, false);
+        if (!unorm && !pre && !f16dst)          MXD(false, false, false, true);
+        if (!unorm && !pre)                     MXD(false, true, false, true);
+        return NULL;
+    }
+    if (unorm && f16dst)    MXD(true, true, false, false);
+    if (unorm)              MXD(true, false, false, false);
+    if (f16dst)             MXD(false, true, false, false);
+    MXD(false, false, false, false);
+#undef MXD
+}
+
 // the pass k_polar_mxd is written for (file header); fills pass->epi for an rgba16 target
 bool plh_polar_mxd_applies(plh_pass *pass)
 {
     const plh_sampler_args &s = pass->s;
-    if (s.mx.enabled != 2 || (s.comp_mask & 0xf) != 0x7 || pass->transpose ||
+    if (!s.pp || s.mx.enabled != 2 || (s.comp_mask & 0xf) != 0x7 || pass->transpose ||
         (s.src.fmt != PLH_FMT_RGBA16F && s.src.fmt != PLH_FMT_RGBA16))
         return false;
     // pre-ops: [an identity PLANE_MAP of a plane that carries r, g, b (changes none)] [LINEARIZE]
@@ -375,6 +401,8 @@ bool plh_polar_mxd_applies(plh_pass *pass)
     int first = pass->num_pre_ops;
     if (first < pass->num_ops && pass->ops[first].kind == PLH_OP_DELINEARIZE)
         first++;
+    if (!mxd_instance(pass))
+        return false;
     if (pass->dst.fmt == PLH_FMT_RGBA16F) {
         const int post = pass->num_ops - first;
         if (post > 1)
@@ -401,31 +429,5 @@ int plh_launch_polar_mxd(hipStream_t stream, const plh_pass *pass)
     int cus = 256;
     (void) plh_stream_device((plh_stream) stream, &cus);
     const int groups = tiles_x * tiles_y < cus ? tiles_x * tiles_y : cus;
-    const bool unorm = pass->s.src.fmt == PLH_FMT_RGBA16, f16dst = pass->dst.fmt == PLH_FMT_RGBA16F;
-    const bool pre = pass->num_pre_ops && pass->ops[pass->num_pre_ops - 1].kind == PLH_OP_LINEARIZE;
-    const bool delin = pass->num_pre_ops < pass->num_ops && pass->ops[pass->num_pre_ops].kind == PLH_OP_DELINEARIZE;
-#define MXD_LAUNCH(U, F, P, D) do { \
-        static uint64_t lds_done; \
-        const int e = plh_kernel_needs_lds((const void *) k_polar_mxd<U, F, P, D>, (plh_stream) stream, shmem, &lds_done); \
-        if (e) \
-            return e; \
-        PLH_LAUNCH_LAST((k_polar_mxd<U, F, P, D>), dim3(groups), dim3(MXD_NT), shmem, stream, *pass); \
-    } while (0)
-    if (pre || delin) {
-        // the passes of a linear-light downscale
-        if (unorm && pre && f16dst && !delin)           MXD_LAUNCH(true, true, true, false);
-        else if (unorm && pre && f16dst)                MXD_LAUNCH(true, true, true, true);
-        else if (unorm && pre && delin)                 MXD_LAUNCH(true, false, true, true);
-        else if (unorm && pre)                          MXD_LAUNCH(true, false, true, false);
-        else if (!unorm && !pre && !f16dst)             MXD_LAUNCH(false, false, false, true);
-        else if (!unorm && !pre)                        MXD_LAUNCH(false, true, false, true);
-        else
-            return -1000;
-    }
-    else if (unorm && f16dst)  MXD_LAUNCH(true, true, false, false);
-    else if (unorm)       MXD_LAUNCH(true, false, false, false);
-    else if (f16dst)      MXD_LAUNCH(false, true, false, false);
-    else                  MXD_LAUNCH(false, false, false, false);
-#undef MXD_LAUNCH
-    return plh_launch_status();
+    return mxd_instance(pass)(dim3(groups), dim3(MXD_NT), shmem, stream, *pass);
 }

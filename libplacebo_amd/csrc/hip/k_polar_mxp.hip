@@ -406,15 +406,19 @@ void k_polar_mxp(const plh_pass p_)
 #undef tp
 
 // Does the persistent kernel take this pass? (Else: k_polar_mx, which handles every shape.)
-bool plh_polar_mxp_applies(const plh_pass *pass)
+bool plh_polar_mxp_applies(plh_pass *pass)
 {
     if (!plh_switch(PLH_SW_MX_PERSIST))
         return false;
     const int fmt = pass->s.src.fmt;
-    if ((pass->s.comp_mask & 0xf) != 0x7 || (fmt != PLH_FMT_RGBA16 && fmt != PLH_FMT_RGBA16F))
+    if (!pass->s.pp || pass->s.mx.enabled != 1 || (pass->s.comp_mask & 0xf) != 0x7 ||
+        (fmt != PLH_FMT_RGBA16 && fmt != PLH_FMT_RGBA16F))
         return false;
+    // (a pass with a map chain is k_polar_mx's, which has the chain's variants: matched as it matches)
+    plh_match_map_chain(pass, true);
     if (!plh_ops_lite(pass, 0, pass->num_pre_ops) || pass->chain.enabled)
         return false;
+    plh_match_fast_epilogue(pass);
     if (!plh_ops_lite(pass, pass->num_pre_ops, pass->num_ops) || !pass->epi.enabled)
         return false;
     // the dither matrix lives in LDS, transposed, and a lane reads eight consecutive rows of it
@@ -422,14 +426,6 @@ bool plh_polar_mxp_applies(const plh_pass *pass)
     if (e.has_dither && (!e.matrix_t || e.size < 8 || e.size > MXP_DMAT_MAX || (pass->frag_y0 & 7)))
         return false;
     return true;
-}
-
-template <int STORE>
-static void launch_mxp(hipStream_t stream, const plh_pass *pass, int groups, size_t shmem)
-{
-    static uint64_t lds_done;
-    (void) plh_kernel_needs_lds((const void *) k_polar_mxp<STORE>, (plh_stream) stream, shmem, &lds_done);
-    PLH_LAUNCH_LAST(k_polar_mxp<STORE>, dim3(groups), dim3(mx_geom<8>::threads), shmem, stream, *pass);
 }
 
 int plh_launch_polar_mxp(hipStream_t stream, const plh_pass *pass)
@@ -442,9 +438,7 @@ int plh_launch_polar_mxp(hipStream_t stream, const plh_pass *pass)
     int cus = 256;
     (void) plh_stream_device((plh_stream) stream, &cus);
     const int groups = min(tiles_x * tiles_y, 2 * cus);
-    if (pass->nt_store)
-        launch_mxp<MXP_STORE_DEFAULT>(stream, pass, groups, shmem);
-    else
-        launch_mxp<0>(stream, pass, groups, shmem);
-    return plh_launch_status();
+    plh_pass_launch_fn *launch = pass->nt_store ? plh_launch_last_lds<k_polar_mxp<MXP_STORE_DEFAULT>>
+                                                : plh_launch_last_lds<k_polar_mxp<0>>;
+    return launch(dim3(groups), dim3(G::threads), shmem, stream, *pass);
 }

@@ -320,6 +320,23 @@ void k_polar_mxr(const plh_pass p_)
     }
 }
 
+// (the largest tile -- two base columns per group, with the PQ pieces -- is below the 64 KiB any kernel may ask for)
+static_assert(MXR_B_BYTES + 3 * (2 * MXR_TBY + 8) * MXR_PITCH + PQSEG_BYTES <= 64 * 1024, "k_polar_mxr: LDS");
+
+// The kernel's instance for the tables' (ratio, group) and the matched ops, or NULL: there is none
+// (the host builds these three pairs only: polar_mx_tables.c, polar_mxr_build)
+static plh_pass_launch_fn *mxr_instance(const plh_pass *pass)
+{
+    const int R = pass->s.mx.ratio, G = pass->s.mx.group;
+#define MXR(RR, GG) return pass->chain.enabled ? plh_launch_last_lds<k_polar_mxr<RR, GG, true>> \
+                                               : plh_launch_last_lds<k_polar_mxr<RR, GG, false>>
+    if (R == 3 && G == 2)   MXR(3, 2);
+    if (R == 3 && G == 1)   MXR(3, 1);
+    if (R == 4 && G == 1)   MXR(4, 1);
+#undef MXR
+    return NULL;
+}
+
 // the pass k_polar_mxr is written for (file header); fills pass->chain / pass->epi
 bool plh_polar_mxr_applies(plh_pass *pass)
 {
@@ -338,25 +355,22 @@ bool plh_polar_mxr_applies(plh_pass *pass)
             return false;
     }
     plh_match_map_chain(pass);
-    if (pass->chain.enabled)
-        return !pass->chain.contrast_recovery && !pass->epi.has_alpha;
-    plh_match_fast_epilogue(pass);
-    return pass->epi.enabled && !pass->epi.has_alpha;
+    if (!pass->chain.enabled)
+        plh_match_fast_epilogue(pass);
+    const bool ops = pass->chain.enabled ? !pass->chain.contrast_recovery : pass->epi.enabled;
+    return ops && !pass->epi.has_alpha && mxr_instance(pass);
 }
 
 int plh_launch_polar_mxr(hipStream_t stream, const plh_pass *pass)
 {
     const int R = pass->s.mx.ratio, G = pass->s.mx.group;
-    if (G != 1 && G != 2)
-        return -1000;
     const int nbx = (pass->width - 1 + pass->s.mx.sx) / R + 1, nby = (pass->height - 1 + pass->s.mx.sy) / R + 1;
     const int tbx = MXR_TSX / G;
     const int tiles = ((nbx + tbx - 1) / tbx) * ((nby + MXR_TBY - 1) / MXR_TBY);
     size_t shmem = MXR_B_BYTES + (size_t) 3 * (G * MXR_TBY + 8) * MXR_PITCH;
-    const bool chain = pass->chain.enabled;
     const plh_pass *arg = pass;
     plh_pass local;
-    if (chain && pass->chain.pq_seg) {
+    if (pass->chain.enabled && pass->chain.pq_seg) {
         // the PQ pair as piecewise cubics in LDS (pqseg.hiph)
         local = *pass;
         local.chain.pq_seg_rshift = 0;
@@ -365,17 +379,5 @@ int plh_launch_polar_mxr(hipStream_t stream, const plh_pass *pass)
             shmem += PQSEG_BYTES;
         arg = &local;
     }
-#define MXR_LAUNCH(RR, GG, CH) PLH_LAUNCH_LAST((k_polar_mxr<RR, GG, CH>), dim3(tiles), dim3(MXR_NT), shmem, stream, *arg)
-    if (G == 2 && R == 3 && chain)  MXR_LAUNCH(3, 2, true);
-    else if (G == 2 && R == 3)      MXR_LAUNCH(3, 2, false);
-    else if (G == 2)
-        return -1000;
-    else if (R == 3 && chain)       MXR_LAUNCH(3, 1, true);
-    else if (R == 3)                MXR_LAUNCH(3, 1, false);
-    else if (R == 4 && chain)       MXR_LAUNCH(4, 1, true);
-    else if (R == 4)                MXR_LAUNCH(4, 1, false);
-    else
-        return -1000;
-#undef MXR_LAUNCH
-    return plh_launch_status();
+    return mxr_instance(pass)(dim3(tiles), dim3(MXR_NT), shmem, stream, *arg);
 }

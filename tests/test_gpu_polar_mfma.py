@@ -440,3 +440,23 @@ def test_mx_every_tile_is_an_edge_tile(kind, sw, sh, capfd):
     else:
         mx = _traced(capfd, "k_polar_mxr", img, dw, dh, ewa(), True, expect_mx=True)
     one_code(mx, pp)
+
+
+# ---- a shape k_polar_mxd has no instance for goes to k_polar_pp -------------------------------------
+@pytest.mark.parametrize("dst_fmt", ["rgba16hf", "rgba16"])
+def test_mxd_no_instance_for_delinearize_without_linearize(dst_fmt, capfd):
+    """A 2 : 1 EWA downscale, in linear light, of a linear-light rgba16 image to a gamma target: the
+    pass reads unorm texels with no LINEARIZE in front (they are linear already) and has a
+    DELINEARIZE behind the taps. k_polar_mxd has the geometry's tables but no instance for that op
+    shape, so its `applies` says no and k_polar_pp takes the pass, with the matrix pipe on or off:
+    the same kernel, the same bits. (With disable_linear_scaling, ewa_down(), the renderer
+    delinearises such an image IN FRONT of the taps -- pre-ops PLANE_MAP DELINEARIZE, post-ops
+    LINEARIZE DELINEARIZE SCALE -- which k_polar_mxd declines by its pre-ops.)"""
+    dw, dh = 18, 10
+    img = util.random_rgba16(2 * dw, 2 * dh, seed=5)
+    params = pl.render_params("fast", downscaler=pl.filter_config("ewa_lanczos"))
+    kw = dict(dst_fmt=dst_fmt, image_kw=dict(color=pl.color_space(transfer="linear")))
+    mx = _traced(capfd, "k_polar_pp", img, dw, dh, params, True, **kw)
+    pp = _traced(capfd, "k_polar_pp", img, dw, dh, params, False, **kw)
+    assert np.array_equal(mx.view(np.uint16), pp.view(np.uint16))
+    assert pp[..., :3].astype(np.float32).std() > 0.01

@@ -139,6 +139,19 @@ def test_polar_downscale_widened_gather_order(gpu):
     util.assert_polar_equal(got, ref)
 
 
+def test_polar_steep_downscale_tile_above_64k(gpu, capfd):
+    # ratio 0.25 -> blur 4 -> radius 12.6, bound 13: the per-pixel kernel's LDS tile of one row of
+    # lanes is 156 x 60 f16 texels, 2048 + 156 * 60 * 8 = 76928 bytes -- above the 64 KiB a kernel may
+    # ask for without opting in (devmath.hiph: plh_launch_needs_lds). k_polar_pp's tables do not fit
+    # at this ratio, so k_polar takes the pass.
+    src = util.random_rgba16(128, 96, seed=5)
+    with util.kernel_trace(capfd) as kernels:
+        got = polar_pipeline(gpu, src, 32, 24)
+    assert [k for k in kernels if k.startswith("k_polar")] == ["k_polar"], kernels
+    ref = polar_oracle(src, 32, 24, orc.ewa_lanczos(blur=4.0))
+    util.assert_polar_equal(got, ref)
+
+
 def test_polar_antiring(gpu):
     src = util.random_rgba16(64, 48, seed=9)
     got = polar_pipeline(gpu, src, 128, 96, antiring=0.8)
