@@ -1,9 +1,10 @@
 /*
- * libplacebo-hip: ICC profile handles referred to by pl_frame / pl_render_params.
- * Types of the reference's src/include/libplacebo/shaders/icc.h (:29-95). ICC colour
- * management needs lcms2, which this build does not have (the reference compiles the same
- * way without PL_HAVE_LCMS: pl_icc_open fails); a frame carrying an `icc` object or a
- * `profile` is rendered from its pl_color_space alone, and a warning is logged once.
+ * libplacebo-hip: ICC colour management (the reference's src/include/libplacebo/shaders/icc.h).
+ * Profiles are interpreted by LittleCMS 2, which is loaded at run time (liblcms2.so.2) on the
+ * first pl_icc_open: no header and no link-time dependency. Where it cannot be loaded the
+ * entry points behave like the reference's compiled without PL_HAVE_LCMS (pl_icc_open fails
+ * and says why), and a frame carrying an `icc` object or a `profile` is rendered from its
+ * pl_color_space alone, with a warning logged once.
  */
 #ifndef LIBPLACEBO_SHADERS_ICC_H_
 #define LIBPLACEBO_SHADERS_ICC_H_
@@ -41,8 +42,11 @@ typedef const struct pl_icc_object_t {
 #define pl_icc_params(...) (&(struct pl_icc_params) { PL_ICC_DEFAULTS __VA_ARGS__ })
 PL_API extern const struct pl_icc_params pl_icc_default_params;
 
-// The entry points (icc.h:97-131), with the behaviour of a libplacebo built without lcms2
-// (src/shaders/icc.c:802-836): open and update fail and log why, nothing else is reachable.
+// The entry points (icc.h:97-131). pl_icc_open: only RGB profiles; NULL on failure (message
+// logged). pl_icc_update: the same profile (by signature) under the same parameters keeps the
+// object, under other parameters reopens it in place; another profile replaces it.
+// pl_icc_decode: profile -> linear light in the profile's containing primaries (*out_csp);
+// pl_icc_encode: the inverse. `lut` holds the direction's 3D table on the device.
 PL_API pl_icc_object pl_icc_open(pl_log log, const struct pl_icc_profile *profile,
                                  const struct pl_icc_params *params);
 PL_API void pl_icc_close(pl_icc_object *icc);

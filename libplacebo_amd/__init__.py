@@ -319,6 +319,15 @@ class Shader:
         self._keep.append(lut)
         lib().pl_shader_custom_lut(self.sh, C.byref(lut), C.byref(state_obj.slot))
 
+    def icc_decode(self, icc, state_obj):
+        """pl_icc_decode; returns the colour space the shader is left in"""
+        out = capi.ColorSpace()
+        lib().pl_icc_decode(self.sh, icc.ptr, C.byref(state_obj.slot), C.byref(out))
+        return out
+
+    def icc_encode(self, icc, state_obj):
+        lib().pl_icc_encode(self.sh, icc.ptr, C.byref(state_obj.slot))
+
     def cone_distort(self, csp, cone_params):
         lib().pl_shader_cone_distort(self.sh, csp, C.byref(cone_params))
 
@@ -505,10 +514,91 @@ class HipGpu:
         self.close()
 
 
+# ---- shaders/icc.h -------------------------------------------------------------------------
+INTENT_AUTO, INTENT_PERCEPTUAL, INTENT_RELATIVE_COLORIMETRIC = -1, 0, 1
+INTENT_SATURATION, INTENT_ABSOLUTE_COLORIMETRIC = 2, 3
+
+
+def icc_profile(data):
+    """struct pl_icc_profile around `data` (bytes), signature computed; keeps the bytes alive"""
+    buf = C.create_string_buffer(data, max(len(data), 1))
+    prof = capi.IccProfile(C.cast(buf, C.c_void_p), len(data), 0)
+    lib().pl_icc_profile_compute_signature(C.byref(prof))
+    prof._keep = buf
+    return prof
+
+
+def icc_params(intent=INTENT_RELATIVE_COLORIMETRIC, size=(0, 0, 0), max_luma=203.0,
+               force_bpc=False, cache=None):
+    return capi.IccParams(intent=intent, size_r=size[0], size_g=size[1], size_b=size[2],
+                          max_luma=max_luma, force_bpc=force_bpc, cache=cache)
+
+
+_ICC_API = {}
+
+
+def icc_api():
+    """pl_icc_open / _update / _close with prototypes of their own (the attributes of the shared
+    CDLL are anybody's to retype): a dict of callables"""
+    if not _ICC_API:
+        P, vp, obj = C.POINTER, C.c_void_p, C.POINTER(capi.IccObject)
+        for name, res, args in (
+            ("pl_icc_open", obj, (vp, P(capi.IccProfile), P(capi.IccParams))),
+            ("pl_icc_close", None, (P(obj),)),
+            ("pl_icc_update", C.c_bool, (vp, P(obj), P(capi.IccProfile), P(capi.IccParams))),
+        ):
+            _ICC_API[name] = C.CFUNCTYPE(res, *args)((name, lib()))
+    return _ICC_API
+
+
+class Icc:
+    """A pl_icc_object opened from profile bytes; raises ValueError where pl_icc_open fails."""
+
+    def __init__(self, profile_bytes, log=None, **params):
+        self.profile = icc_profile(profile_bytes)
+        self.log = log
+        self.ptr = icc_api()["pl_icc_open"](log, C.byref(self.profile), C.byref(icc_params(**params)))
+        if not self.ptr:
+            raise ValueError("pl_icc_open failed")
+
+    def update(self, profile_bytes=None, **params):
+        """pl_icc_update: with other bytes, other parameters, or both"""
+        if profile_bytes is not None:
+            self.profile = icc_profile(profile_bytes)
+        ptr = self.ptr if self.ptr else C.POINTER(capi.IccObject)()
+        ok = icc_api()["pl_icc_update"](self.log, C.byref(ptr), C.byref(self.profile),
+                                        C.byref(icc_params(**params)))
+        self.ptr = ptr
+        return ok
+
+    def __getattr__(self, name):    # params, signature, csp, gamma, containing_primaries
+        if name == "ptr" or not self.__dict__.get("ptr"):
+            raise AttributeError(name)
+        return getattr(self.ptr.contents, name)
+
+    def address(self):
+        return C.cast(self.ptr, C.c_void_p).value
+
+    def lut(self, encode=False):
+        """the 3D table of one direction as uint16 [size_b][size_g][size_r][4] (no device)"""
+        n = lib().plh_test_icc_lut(self.ptr, int(encode), None)
+        p = self.params
+        out = np.zeros((p.size_b, p.size_g, p.size_r, 4), np.uint16)
+        assert n == out.size // 4
+        lib().plh_test_icc_lut(self.ptr, int(encode), out.ctypes.data)
+        return out
+
+    def close(self):
+        if self.__dict__.get("ptr"):
+            icc_api()["pl_icc_close"](C.byref(self.ptr))
+        self.ptr = None
+
+
 # ---- renderer.h ----------------------------------------------------------------------------
 def frame(tex, repr_=None, color=None, crop=None, components=None, mapping=None,
-          flipped=False):
-    """A single-plane pl_frame around `tex` (a Texture)."""
+          flipped=False, icc=None, profile=None):
+    """A single-plane pl_frame around `tex` (a Texture). icc: an Icc; profile: what icc_profile
+    returns (the older pl_frame.profile interface: the renderer opens it itself)."""
     f = capi.Frame(num_planes=1)
     pl_ = f.planes[0]
     pl_.texture = tex.ptr
@@ -522,6 +612,11 @@ def frame(tex, repr_=None, color=None, crop=None, components=None, mapping=None,
     f.color = color if color is not None else color_space("bt709", "srgb")
     if crop is not None:
         f.crop = capi.Rect2df(*crop)
+    if icc is not None:
+        f.icc = icc.address()
+    if profile is not None:
+        f.profile = profile
+        f._keep_profile = profile
     return f
 
 

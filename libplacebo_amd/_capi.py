@@ -630,10 +630,15 @@ class Hook(C.Structure):
 
 
 # ---- options.h ------------------------------------------------------------------------------
-class IccParams(C.Structure):  # shaders/icc.h: stored by pl_options, never used (no ICC engine)
+class IccParams(C.Structure):  # shaders/icc.h
     _fields_ = [("intent", C.c_int), ("size_r", C.c_int), ("size_g", C.c_int), ("size_b", C.c_int),
                 ("max_luma", C.c_float), ("force_bpc", C.c_bool), ("cache", C.c_void_p),
                 ("cache_priv", C.c_void_p), ("cache_save", C.c_void_p), ("cache_load", C.c_void_p)]
+
+
+class IccObject(C.Structure):  # struct pl_icc_object_t
+    _fields_ = [("params", IccParams), ("signature", C.c_uint64), ("csp", ColorSpace),
+                ("gamma", C.c_float), ("containing_primaries", C.c_int)]
 
 
 class Options(C.Structure):
@@ -790,6 +795,17 @@ def declare(lib):
     fn("pl_lut_parse_cube", P(CustomLut), vp, C.c_char_p, C.c_size_t)
     fn("pl_lut_free", None, P(P(CustomLut)))
     fn("pl_shader_custom_lut", None, vp, P(CustomLut), P(vp))
+    fn("pl_icc_open", P(IccObject), vp, P(IccProfile), P(IccParams))
+    fn("pl_icc_close", None, P(P(IccObject)))
+    fn("pl_icc_update", C.c_bool, vp, P(P(IccObject)), P(IccProfile), P(IccParams))
+    fn("pl_icc_decode", None, vp, P(IccObject), P(vp), P(ColorSpace))
+    fn("pl_icc_encode", None, vp, P(IccObject), P(vp))
+    fn("pl_icc_profile_compute_signature", None, P(IccProfile))
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "plh_test_icc_lut"):
+        # test hooks (shader_icc.c): the 3D table of one direction without a device (texels; out
+        # NULL: only the count), and the number of tables generated so far
+        fn("plh_test_icc_lut", C.c_size_t, P(IccObject), C.c_int, vp)
+        fn("plh_test_icc_fills", C.c_int)
     fn("pl_find_tone_map_function", vp, C.c_char_p)
     fn("pl_find_gamut_map_function", vp, C.c_char_p)
     fn("pl_color_space_nominal_luma_ex", None, vp)
@@ -878,7 +894,8 @@ MIRRORS = {
     "struct pl_peak_detect_params": PeakDetectParams, "struct pl_color_map_params": ColorMapParams,
     "struct pl_color_map_args": ColorMapArgs, "struct pl_plane": Plane,
     "struct pl_plane_data": PlaneData, "struct pl_custom_lut": CustomLut,
-    "struct pl_icc_profile": IccProfile, "struct pl_av1_grain_data": Av1GrainData,
+    "struct pl_icc_profile": IccProfile, "struct pl_icc_params": IccParams,
+    "struct pl_icc_object_t": IccObject, "struct pl_av1_grain_data": Av1GrainData,
     "struct pl_h274_grain_data": H274GrainData, "struct pl_film_grain_data": FilmGrainData,
     "struct pl_frame": Frame, "struct pl_frame_mix": FrameMix,
     "struct pl_source_frame": SourceFrame, "struct pl_queue_params": QueueParams,

@@ -293,6 +293,14 @@ enum plh_op_kind {
     // behind CLIP_MARK: the tone curve of TONE_MAP (op i - i0), plotted over the same rect
     // (f[0..3]); f[4..8] = input min, max, avg, output min, max (PQ); f[9] = alpha
     PLH_OP_VIZ_TONE,
+    // pl_icc_decode / pl_icc_encode (shaders/icc.c:698-800), like the Dolby Vision ops only in the
+    // generic pass kernel's DOVI variant. ptr = rgba16 3-D table (red fastest), i0 i1 i2 = sizes,
+    // looked up by tetrahedral interpolation as CUSTOM_LUT does (exact texel fetches, clamped).
+    //   decode: rgb = lut(rgb); rgb = f[3] * pow(f[0] * rgb + f[1], f[2])      (a, b, gamma, scale)
+    //   encode: rgb = f[2] * pow(f[0] * max(rgb, 0), f[1]) - f[3]; rgb = lut(rgb)
+    //           (1 / scale, 1 / gamma, 1 / a, b / a)
+    PLH_OP_ICC_DECODE,
+    PLH_OP_ICC_ENCODE,
 };
 
 // the ops that exist in the generic pass kernel's DOVI / VIZ variants only
@@ -303,7 +311,7 @@ static inline int plh_op_is_viz(int kind)
 static inline int plh_op_generic_only(int kind)
 {
     return kind == PLH_OP_DOVI_RESHAPE || kind == PLH_OP_DOVI_LMS || kind == PLH_OP_CORNER_ROUND ||
-           plh_op_is_viz(kind);
+           kind == PLH_OP_ICC_DECODE || kind == PLH_OP_ICC_ENCODE || plh_op_is_viz(kind);
 }
 
 // pl_reshape_data as the reshaping stage reads it (pl_shader_dovi_reshape packs the same)

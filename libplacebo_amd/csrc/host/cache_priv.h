@@ -15,6 +15,7 @@ enum {
     PLH_CACHE_KEY_SH_LUT    = UINT64_C(0x2206183d320352c6), // host-generated shader LUTs
     PLH_CACHE_KEY_DITHER    = UINT64_C(0x6fed75eb6dce86cb), // blue-noise matrix
     PLH_CACHE_KEY_GAMUT_LUT = UINT64_C(0x6109e47f15d478b1), // gamut-mapping 3D-LUT
+    PLH_CACHE_KEY_ICC_3DLUT = UINT64_C(0xff703a6dd8a996f6), // ICC 3D-LUT (seed of its signature)
 };
 
 // SipHash-2-4 under the reference's fixed key (what pl_mem_hash is without xxhash)

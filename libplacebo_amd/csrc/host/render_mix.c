@@ -333,6 +333,7 @@ static bool cache_fill(struct frame_job *outer, struct mix_entry *e, const struc
         e->params_digest = digest;
         e->crop = image->crop;
         e->color = job.img.color;
+        e->profile = ptarget->profile;
         e->repr = job.img.repr;
         e->comps = job.img.comps;
     }
@@ -500,7 +501,8 @@ bool pl_render_image_mix(pl_renderer rr, const struct pl_frame_mix *mix,
             if (usable && strict) {
                 usable = e->tex->params.w == out_w && e->tex->params.h == out_h &&
                          same_rect(e->crop, image->crop) && e->params_digest == digest &&
-                         pl_color_space_equal(&e->color, &job.target.color);
+                         pl_color_space_equal(&e->color, &job.target.color) &&
+                         pl_icc_profile_equal(&e->profile, &ptarget->profile);
             }
             if (!usable && uncached)
                 goto single;

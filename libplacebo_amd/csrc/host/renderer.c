@@ -24,8 +24,9 @@
  * leaves the image resident, one that appends ops leaves it recorded, and every decision below
  * (try_fused_polar, is_pure_copy, the chain matcher in the dispatch) looks at the image as it finds it.
  *
- * Outside the scope of this backend: ICC profiles, film grain (ignored with an error
- * bit / warning); hooks made from GLSL text (pl_mpv_user_shader_parse returns NULL).
+ * Outside the scope of this backend: film grain (ignored with an error bit / warning);
+ * hooks made from GLSL text (pl_mpv_user_shader_parse returns NULL). ICC profiles are interpreted
+ * where LittleCMS can be loaded (shader_icc.c), and ignored with a warning where it cannot.
  */
 #include <math.h>
 #include <stdlib.h>
@@ -144,6 +145,10 @@ void pl_renderer_destroy(pl_renderer *ptr)
     }
     for (int i = 0; i < RR_LUT_COUNT; i++)
         pl_shader_obj_destroy(&rr->lut_state[i]);
+    for (int i = 0; i < RR_ICC_COUNT; i++) {
+        pl_shader_obj_destroy(&rr->icc_state[i]);
+        pl_icc_close(&rr->icc_fallback[i].icc);
+    }
     pl_shader_obj_destroy(&rr->tone_map_state);
     pl_shader_obj_destroy(&rr->dither_state);
     pl_dispatch_destroy(&rr->dp);
@@ -628,7 +633,7 @@ bool plh_params_supported(pl_renderer rr, const struct pl_render_params *p)
 // things a frame may carry that are not rendered here: say so once, keep going
 static void note_ignored_members(pl_renderer rr, const struct pl_frame *f)
 {
-    if ((f->icc || f->profile.data) && !rr->warned_icc) {
+    if ((f->icc || f->profile.data) && !rr->warned_icc && !plh_icc_available()) {
         rr->warned_icc = true;
         RR_LOG(rr, PL_LOG_WARN, "ICC profiles are not interpreted by this build (no lcms2): "
                "rendering from the frame's pl_color_space");
@@ -638,6 +643,39 @@ static void note_ignored_members(pl_renderer rr, const struct pl_frame *f)
         raise(rr, PL_RENDER_ERR_FILM_GRAIN, PL_LOG_WARN,
               "Film grain synthesis is not part of this backend");
     }
+}
+
+// pl_frame.profile, the older interface (icc_fallback, :3235-3254): opened with the default
+// parameters into the renderer's own object, which the frame then carries as its `icc`
+static void icc_fallback(pl_renderer rr, struct pl_frame *frame, int which)
+{
+    if (!frame->icc && !frame->profile.data)
+        return;
+    if (!plh_icc_available()) {
+        frame->icc = NULL;      // (nothing that could be an object; note_ignored_members has warned)
+        return;
+    }
+    if (frame->icc)
+        return;
+    if (rr->icc_fallback[which].error && rr->icc_fallback[which].error == frame->profile.signature)
+        return;
+    if (pl_icc_update(rr->log, &rr->icc_fallback[which].icc, &frame->profile, NULL)) {
+        frame->icc = rr->icc_fallback[which].icc;
+    } else {
+        RR_LOG(rr, PL_LOG_WARN, "Failed opening ICC profile... ignoring");
+        rr->icc_fallback[which].error = frame->profile.signature;
+    }
+}
+
+// a frame with a profile has the profile's colour space (:3268-3281)
+static void force_icc_color(struct pl_frame *frame)
+{
+    if (!frame->icc)
+        return;
+    frame->color.primaries = frame->icc->containing_primaries;
+    frame->color.hdr = frame->icc->csp.hdr;
+    if (frame->icc->csp.transfer)
+        frame->color.transfer = frame->icc->csp.transfer;
 }
 
 void plh_job_end(struct frame_job *job)
@@ -744,6 +782,10 @@ bool plh_job_begin(struct frame_job *job, bool acquire_image)
     }
     note_ignored_members(rr, &job->image);
     note_ignored_members(rr, &job->target);
+    icc_fallback(rr, &job->image, RR_ICC_IMAGE);
+    icc_fallback(rr, &job->target, RR_ICC_TARGET);
+    force_icc_color(&job->image);
+    force_icc_color(&job->target);
 
     job->caps.max_shmem = rr->gpu->glsl.max_shmem_size;
     job->caps.sampling_broken = rr->errors & PL_RENDER_ERR_SAMPLING;
@@ -778,8 +820,13 @@ void pl_frames_infer(pl_renderer rr, struct pl_frame *image, struct pl_frame *ta
                                                 tref->params.h, target->rotation);
     image->crop = geo.src;
     target->crop = geo.dstf;
+    if (rr) {
+        icc_fallback(rr, image, RR_ICC_IMAGE);
+        icc_fallback(rr, target, RR_ICC_TARGET);
+    }
+    force_icc_color(image);
+    force_icc_color(target);
     rp_complete_frames(image, target);
-    (void) rr;
 }
 
 void pl_frame_set_chroma_location(struct pl_frame *frame, enum pl_chroma_location loc)
@@ -942,6 +989,8 @@ static bool append_plane_map(pl_shader sh, const struct pl_plane *plane, bool on
              (unsigned) dest, neutral_luma, neutral_chroma);
     return true;
 }
+
+static bool generic_can_run(const struct frame_job *job, const pl_shader sh);
 
 bool plh_stage_read(struct frame_job *job)
 {
@@ -1112,6 +1161,20 @@ bool plh_stage_read(struct frame_job *job)
     }
     if (lut == PL_LUT_NORMALIZED)
         pl_shader_custom_lut(sh, image->lut, &rr->lut_state[RR_LUT_IMAGE]);
+
+    // The image's profile (:1948-1953), which a main PL_LUT_CONVERSION LUT overrides. Its op lives
+    // in the generic kernel only: a pending pass that kernel cannot run (a debanded plane) is
+    // stored first, unrounded, as for a Dolby Vision plane
+    if (image->icc && !(params->lut && params->lut_type == PL_LUT_CONVERSION)) {
+        if (!generic_can_run(job, sh) && job->caps.fbo[4]) {
+            img->store_as = pl_find_named_fmt(rr->gpu, "rgba32f");
+            if (!plh_work_texture(job, img))
+                return false;
+            sh = plh_work_shader(job, img);
+        }
+        pl_shader_set_alpha(sh, &img->repr, PL_ALPHA_INDEPENDENT);
+        pl_icc_decode(sh, image->icc, &rr->icc_state[RR_ICC_IMAGE], &img->color);
+    }
 
     // transparent regions must not bleed into opaque ones while filtering
     pl_shader_set_alpha(sh, &img->repr, PL_ALPHA_PREMULTIPLIED);
@@ -1401,8 +1464,6 @@ static bool apply_params_lut(struct frame_job *job, pl_shader sh, bool *prelinea
     return true;
 }
 
-static bool generic_can_run(const struct frame_job *job, const pl_shader sh);
-
 // pl_color_map_params.show_clipping / .visualize_lut: the ops they record exist in one variant of
 // the generic pass kernel only (plh_device.h)
 static bool wants_diagnostics(const struct pl_color_map_params *cm)
@@ -1452,6 +1513,10 @@ void plh_stage_colors(struct frame_job *job)
         if (job->peak_pending && !plh_work_texture(job, img))
             return;
         pl_tex features = make_feature_map(job);
+        // a target profile is entered in linear light (:2250-2252)
+        struct pl_color_space target_csp = target->color;
+        if (target->icc)
+            target_csp.transfer = PL_COLOR_TRC_LINEAR;
         // the diagnostics go where the generic kernel's variant for them can run: a pending pass
         // it cannot (a scaler with a kernel of its own, a measurement) is stored first, as for
         // rounded corners. (Whether the request reaches the full path at all is the plan's
@@ -1459,7 +1524,9 @@ void plh_stage_colors(struct frame_job *job)
         // on a path nobody measures.)
         // Stored unrounded (rgba32f), like a Dolby Vision plane: what lies outside the plot is then
         // the frame the pass would have rendered itself, not that frame through an f16 rounding.
-        if (wants_diagnostics(cm) && img->rec && !generic_can_run(job, img->rec) && job->caps.fbo[4]) {
+        // (A target profile's op lives in the same kernel and takes the same way.)
+        if ((wants_diagnostics(cm) || target->icc) && img->rec && !generic_can_run(job, img->rec) &&
+            job->caps.fbo[4]) {
             pl_fmt exact = pl_find_named_fmt(rr->gpu, "rgba32f");
             if (exact && (exact->caps & PL_FMT_CAP_STORABLE))
                 img->store_as = exact;
@@ -1469,11 +1536,22 @@ void plh_stage_colors(struct frame_job *job)
         sh = plh_work_shader(job, img);
         pl_shader_color_map_ex(sh, params->color_map_params, pl_color_map_args(
             .src           = image->color,
-            .dst           = target->color,
+            .dst           = target_csp,
             .prelinearized = prelinearized,
             .state         = &rr->tone_map_state,
             .feature_map   = features,
         ));
+        if (target->icc) {
+            // (the tricubic lookup and the profile's op live in different variants of the generic
+            // kernel: the colour map is stored first, unrounded)
+            if (cm && cm->lut3d_tricubic && job->caps.fbo[4]) {
+                img->store_as = pl_find_named_fmt(rr->gpu, "rgba32f");
+                if (!plh_work_texture(job, img))
+                    return;
+                sh = plh_work_shader(job, img);
+            }
+            pl_icc_encode(sh, target->icc, &rr->icc_state[RR_ICC_TARGET]);
+        }
     }
 
     // a target LUT working on RGB acts here; a NATIVE one after the encoding

@@ -6,6 +6,7 @@
 #define PLH_RENDERER_PRIV_H_
 
 #include <libplacebo/renderer.h>
+#include <libplacebo/shaders/icc.h>
 
 #include "render_plan.h"
 #include "shaders_priv.h"
@@ -21,6 +22,7 @@ struct scaler_slot {
 };
 
 enum { RR_LUT_IMAGE, RR_LUT_TARGET, RR_LUT_PARAMS, RR_LUT_COUNT };
+enum { RR_ICC_IMAGE, RR_ICC_TARGET, RR_ICC_COUNT };
 
 // a frame rendered for mixing, kept across vsyncs
 struct mix_entry {
@@ -28,6 +30,7 @@ struct mix_entry {
     uint64_t params_digest;     // of the render params it was produced with
     struct pl_color_space color;
     struct pl_color_repr repr;
+    struct pl_icc_profile profile;  // the target's (deprecated) profile it was produced for
     pl_rect2df crop;
     pl_tex tex;
     int comps;
@@ -55,6 +58,13 @@ struct pl_renderer_t {
     pl_shader_obj tone_map_state;
     pl_shader_obj dither_state;
     pl_shader_obj lut_state[RR_LUT_COUNT];
+    pl_shader_obj icc_state[RR_ICC_COUNT];          // the device tables of pl_icc_decode / _encode
+    // pl_frame.profile (the older interface) opened on the frame's behalf; `error`: the signature
+    // of a profile that failed, not tried again
+    struct {
+        pl_icc_object icc;
+        uint64_t error;
+    } icc_fallback[RR_ICC_COUNT];
     int last_dither_depth;
     bool warned_icc, warned_grain;
     struct plh_overlay_part *osd_parts;     // the overlay being drawn, placed on the plane

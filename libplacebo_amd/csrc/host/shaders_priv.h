@@ -139,6 +139,9 @@ void plh_polar_pp_setup(pl_gpu gpu, pl_log log, void *polar_obj, struct plh_pass
 void plh_peak_pass_launched(pl_gpu gpu, pl_shader_obj state, int on, uint64_t seq, bool recorded);
 plh_event plh_peak_written_event(pl_shader_obj state);
 
+// LittleCMS could be loaded (shader_icc.c); tries to, the first time
+bool plh_icc_available(void);
+
 // the finalized, still-alive shader behind a "#pl_hip_pass <ticket>" line; NULL if there is none
 pl_shader plh_shader_from_glsl(const char *glsl);
 
