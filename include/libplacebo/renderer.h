@@ -258,6 +258,15 @@ PL_API void pl_frame_set_chroma_location(struct pl_frame *frame,
 // true if the frame's crop does not cover its whole reference plane
 PL_API bool pl_frame_is_cropped(const struct pl_frame *frame);
 
+// A target frame for what pl_swapchain_start_frame handed out (swapchain.h, which a caller of this
+// function includes itself): one plane, the frame's `fbo` with its `flipped` flag and the identity
+// component mapping -- as many components as the format has, three at most when
+// `color_repr.alpha` is PL_ALPHA_NONE; `crop` the whole image; `repr` and `color` the frame's
+// `color_repr` and `color_space`.
+struct pl_swapchain_frame;
+PL_API void pl_frame_from_swapchain(struct pl_frame *out_frame,
+                                    const struct pl_swapchain_frame *frame);
+
 // Fill every plane of `frame` with one colour, given as sRGB and converted to the frame's colour
 // space and encoding (renderer.h:672-690 in the reference; premultiplied frames get rgb * alpha).
 // What applications call on a target before / instead of rendering into a part of it.

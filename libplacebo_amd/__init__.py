@@ -925,6 +925,80 @@ class Renderer:
             lib().pl_renderer_destroy(C.byref(self.rr))
 
 
+# ---- swapchain.h / hip_swapchain.h -----------------------------------------------------------
+class Swapchain:
+    """pl_hip_create_swapchain and both sides of it. Textures handed out are borrowed (Texture
+    objects that destroy nothing)."""
+
+    def __init__(self, gpu, width, height, fmt=None, num_images=0, latency=0, alpha="unknown",
+                 host_readback=False):
+        self.gpu = gpu
+        sp = capi.HipSwapchainParams(width=width, height=height, num_images=num_images,
+                                     latency=latency, alpha=ALPHA[alpha],
+                                     host_readback=host_readback)
+        if fmt is not None:
+            sp.format = gpu.fmt(fmt)
+        self.sw = lib().pl_hip_create_swapchain(gpu.hip, C.byref(sp))
+        if not self.sw:
+            raise RuntimeError("pl_hip_create_swapchain failed: " +
+                               "; ".join(m for _, m in gpu.messages[-3:]))
+
+    def latency(self):
+        return lib().pl_swapchain_latency(self.sw)
+
+    def resize(self, width=0, height=0):
+        """pl_swapchain_resize: (ok, width, height) with the size in force"""
+        w, h = C.c_int(width), C.c_int(height)
+        ok = lib().pl_swapchain_resize(self.sw, C.byref(w), C.byref(h))
+        return ok, w.value, h.value
+
+    def colorspace_hint(self, csp=None):
+        lib().pl_swapchain_colorspace_hint(self.sw, C.byref(csp) if csp is not None else None)
+
+    def start_frame(self):
+        """the capi.SwapchainFrame, or None when pl_swapchain_start_frame returned false"""
+        f = capi.SwapchainFrame()
+        return f if lib().pl_swapchain_start_frame(self.sw, C.byref(f)) else None
+
+    def target(self, swframe):
+        """pl_frame_from_swapchain"""
+        f = capi.Frame()
+        lib().pl_frame_from_swapchain(C.byref(f), C.byref(swframe))
+        return f
+
+    def texture(self, ptr):
+        return Texture(self.gpu, ptr, owned=False)
+
+    def submit_frame(self):
+        return lib().pl_swapchain_submit_frame(self.sw)
+
+    def swap_buffers(self):
+        lib().pl_swapchain_swap_buffers(self.sw)
+
+    def acquire(self, timeout_ns=0):
+        """the capi.HipPresented, or None"""
+        out = capi.HipPresented()
+        return out if lib().pl_hip_swapchain_acquire(self.sw, C.byref(out), timeout_ns) else None
+
+    def host_image(self, presented):
+        """a copy of the host_readback frame of an acquired image, in the format's host layout"""
+        tex = presented.tex.contents.params
+        dt, nc = _FMT_DTYPES[tex.format.contents.name.decode()]
+        row = tex.w * nc * np.dtype(dt).itemsize
+        raw = np.ctypeslib.as_array(C.cast(presented.host_ptr, C.POINTER(C.c_uint8)),
+                                    (tex.h, presented.host_pitch))
+        return raw[:, :row].copy().view(dt).reshape(tex.h, tex.w, nc)
+
+    def release(self, tex_ptr, consumer_stream=None):
+        lib().pl_hip_swapchain_release(self.sw, tex_ptr, consumer_stream)
+
+    def destroy(self):
+        if self.sw:
+            sw = self.sw
+            lib().pl_swapchain_destroy(C.byref(sw))
+            self.sw = None
+
+
 # ---- options.h -------------------------------------------------------------------------------
 def option_list():
     """pl_option_list as a list of capi.Opt (pl_option_count entries)"""

@@ -671,6 +671,35 @@ class OptData(C.Structure):
 OPT_ITERATE_CB = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(OptData))
 
 
+# ---- swapchain.h / hip_swapchain.h ---------------------------------------------------------
+class Swapchain(C.Structure):  # struct pl_swapchain_t
+    _fields_ = [("log", C.c_void_p), ("gpu", C.POINTER(Gpu))]
+
+
+class SwapchainFrame(C.Structure):
+    _fields_ = [("fbo", C.POINTER(Tex)), ("flipped", C.c_bool), ("color_repr", ColorRepr),
+                ("color_space", ColorSpace)]
+
+
+class HipSwapchainParams(C.Structure):
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("format", C.POINTER(Fmt)),
+                ("num_images", C.c_int), ("latency", C.c_int), ("alpha", C.c_int),
+                ("host_readback", C.c_bool)]
+
+
+class HipPresented(C.Structure):
+    _fields_ = [("tex", C.POINTER(Tex)), ("seq", C.c_uint64), ("color_repr", ColorRepr),
+                ("color_space", ColorSpace), ("ready_event", C.c_void_p),
+                ("host_ptr", C.c_void_p), ("host_pitch", C.c_size_t)]
+
+
+SWAPCHAIN_FUNCTIONS = ("pl_swapchain_destroy", "pl_swapchain_latency", "pl_swapchain_resize",
+                       "pl_swapchain_colorspace_hint", "pl_swapchain_start_frame",
+                       "pl_swapchain_submit_frame", "pl_swapchain_swap_buffers",
+                       "pl_frame_from_swapchain", "pl_hip_create_swapchain",
+                       "pl_hip_swapchain_acquire", "pl_hip_swapchain_release")
+
+
 # enum pl_hook_stage, in the order the renderer visits the stages
 HOOK_STAGES = ("RGB_INPUT", "LUMA_INPUT", "CHROMA_INPUT", "ALPHA_INPUT", "XYZ_INPUT",
                "CHROMA_SCALED", "ALPHA_SCALED", "NATIVE", "RGB", "LINEAR", "SIGMOID",
@@ -861,6 +890,20 @@ def declare(lib):
         # (n_axis, n_across, row_size, pos[4][2], dir): may k_ortho_fast's one reflection serve a
         # mirrored pass (shader_sampling.c)
         fn("plh_test_ortho_one_reflection", C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float), C.c_int)
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "pl_hip_create_swapchain"):
+        # swapchain.h, hip_swapchain.h and renderer.h's pl_frame_from_swapchain
+        sw = P(Swapchain)
+        fn("pl_swapchain_destroy", None, P(sw))
+        fn("pl_swapchain_latency", C.c_int, sw)
+        fn("pl_swapchain_resize", C.c_bool, sw, P(C.c_int), P(C.c_int))
+        fn("pl_swapchain_colorspace_hint", None, sw, P(ColorSpace))
+        fn("pl_swapchain_start_frame", C.c_bool, sw, P(SwapchainFrame))
+        fn("pl_swapchain_submit_frame", C.c_bool, sw)
+        fn("pl_swapchain_swap_buffers", None, sw)
+        fn("pl_frame_from_swapchain", None, P(Frame), P(SwapchainFrame))
+        fn("pl_hip_create_swapchain", sw, P(Hip), P(HipSwapchainParams))
+        fn("pl_hip_swapchain_acquire", C.c_bool, sw, P(HipPresented), C.c_uint64)
+        fn("pl_hip_swapchain_release", None, sw, P(Tex), vp)
     return lib
 
 
@@ -913,4 +956,11 @@ MIRRORS_CUSTOM = {
 # the same for options.h, against tests/golden/abi_layout_options.json (tests/test_options.py)
 MIRRORS_OPTIONS = {
     "struct pl_options_t": Options, "struct pl_opt_t": Opt, "struct pl_opt_data_t": OptData,
+}
+
+# the same for swapchain.h + hip_swapchain.h, against tests/golden/abi_layout_swapchain.json
+# (tests/test_swapchain_abi.py)
+MIRRORS_SWAPCHAIN = {
+    "struct pl_swapchain_t": Swapchain, "struct pl_swapchain_frame": SwapchainFrame,
+    "struct pl_hip_swapchain_params": HipSwapchainParams, "struct pl_hip_presented": HipPresented,
 }

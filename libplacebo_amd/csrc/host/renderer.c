@@ -33,6 +33,7 @@
 #include <string.h>
 
 #include <libplacebo/shaders/deinterlacing.h>
+#include <libplacebo/swapchain.h>
 
 #include "renderer_priv.h"
 
@@ -2270,4 +2271,26 @@ size_t plh_test_plan(const struct pl_frame *image, const struct pl_frame *target
         out[n] = '\0';
     }
     return len;
+}
+
+// The target frame of a swapchain image (swapchain.h): the fbo as the only plane, its components
+// in their own order -- without the fourth where the consumer ignores alpha -- the whole image as
+// the crop, encoding and colour space as the swapchain states them.
+void pl_frame_from_swapchain(struct pl_frame *out_frame, const struct pl_swapchain_frame *frame)
+{
+    const struct pl_tex_params *image = &frame->fbo->params;
+    const int limit = frame->color_repr.alpha == PL_ALPHA_NONE ? 3 : 4;
+
+    memset(out_frame, 0, sizeof(*out_frame));
+    out_frame->repr = frame->color_repr;
+    out_frame->color = frame->color_space;
+    out_frame->crop.x1 = image->w;
+    out_frame->crop.y1 = image->h;
+
+    struct pl_plane *plane = &out_frame->planes[out_frame->num_planes++];
+    plane->texture = frame->fbo;
+    plane->flipped = frame->flipped;
+    for (int c = 0; c < 4; c++)
+        plane->component_mapping[c] = c;
+    plane->components = PL_MIN(image->format->num_components, limit);
 }

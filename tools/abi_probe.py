@@ -14,6 +14,7 @@ cross the C ABI to be layout-compatible with libplacebo's.
     tools/abi_probe.py golden          # rewrite tests/golden/abi_layout.json from the reference
     tools/abi_probe.py golden-custom   # the same for shaders/custom.h -> abi_layout_custom.json
     tools/abi_probe.py golden-options  # the same for options.h -> abi_layout_options.json
+    tools/abi_probe.py golden-swapchain  # swapchain.h (+ hip_swapchain.h) -> abi_layout_swapchain.json
 
 Headers listed in GROUPS have a table (and a golden file) of their own: every other command and
 function looks at the main set unless told otherwise, so that a header added later does not change
@@ -35,7 +36,7 @@ REF = os.environ.get("PL_REFERENCE", "/root/reference")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "abi_layout.json")
 
 # headers that only exist on this backend (no reference counterpart)
-OWN_HEADERS = {"libplacebo/hip.h"}
+OWN_HEADERS = {"libplacebo/hip.h", "libplacebo/hip_swapchain.h"}
 
 # headers probed as a group of their own: group -> (headers, golden file)
 GROUPS = {
@@ -43,6 +44,8 @@ GROUPS = {
                os.path.join(ROOT, "tests", "golden", "abi_layout_custom.json")),
     "options": ({"libplacebo/options.h"},
                 os.path.join(ROOT, "tests", "golden", "abi_layout_options.json")),
+    "swapchain": ({"libplacebo/swapchain.h", "libplacebo/hip_swapchain.h"},
+                  os.path.join(ROOT, "tests", "golden", "abi_layout_swapchain.json")),
 }
 GROUPED_HEADERS = set().union(*(g[0] for g in GROUPS.values()))
 
