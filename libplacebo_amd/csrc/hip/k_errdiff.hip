@@ -103,6 +103,7 @@ extern "C" int plh_launch_errdiff(plh_stream stream, const plh_errdiff_args *arg
         return -1000;
     if (const int e = plh_launch_needs_lds<k_errdiff>((hipStream_t) stream, shmem))
         return e;
+    plh_trace_kernel("k_errdiff");
     hipLaunchKernelGGL(k_errdiff, dim3(1), dim3(args->block_size), shmem, (hipStream_t) stream,
                        *args);
     return plh_launch_status();

@@ -1703,11 +1703,17 @@ static void append_swizzle(pl_shader sh, int comps, const int mapping[4], bool f
 }
 
 // Run `*sh` into an intermediate, diffuse the quantisation error over it (one workgroup, the
-// whole image's error ring in LDS), and continue from the result (:2282-2344)
-static bool run_error_diffusion(struct frame_job *job, pl_shader *sh, int depth, int comps,
-                                int w, int h)
+// whole image's error ring in LDS), and continue from the result (:2282-2344).
+// The intermediate of a plane with fewer than four components holds `components` values: the
+// plane's own, so they are moved to the front for the diffusion and back to the image's order behind
+// it, where the output stage's swizzle expects them. (The reference stores the colour as it is,
+// :2322-2337: a chroma plane, whose mapping reads components 1 and 2, then comes back without what
+// a one- or two-component intermediate never held.)
+static bool run_error_diffusion(struct frame_job *job, pl_shader *sh, int depth,
+                                const struct pl_plane *plane, int w, int h)
 {
     pl_renderer rr = job->rr;
+    const int comps = plane->components;
     pl_fmt fmt = job->caps.fbo[comps];
     if (!fmt || !(fmt->caps & PL_FMT_CAP_STORABLE)) {
         raise(rr, PL_RENDER_ERR_ERROR_DIFFUSION, PL_LOG_ERR,
@@ -1728,6 +1734,15 @@ static bool run_error_diffusion(struct frame_job *job, pl_shader *sh, int depth,
         return false;
     }
 
+    int back[4] = { -1, -1, -1, -1 };
+    if (comps < 4) {
+        append_swizzle(*sh, comps, plane->component_mapping, false);
+        for (int c = 0; c < comps; c++) {
+            if (plane->component_mapping[c] >= 0)
+                back[plane->component_mapping[c]] = c;
+        }
+    }
+
     bool ok = pl_dispatch_finish(rr->dp, pl_dispatch_params( .shader = sh, .target = ed.input_tex ));
     if (ok) {
         ok = pl_dispatch_compute(rr->dp, pl_dispatch_compute_params(
@@ -1738,6 +1753,8 @@ static bool run_error_diffusion(struct frame_job *job, pl_shader *sh, int depth,
     }
     *sh = pl_dispatch_begin(rr->dp);
     pl_shader_sample_direct(*sh, pl_sample_src( .tex = ok ? ed.output_tex : ed.input_tex ));
+    if (comps < 4)
+        append_swizzle(*sh, 4, back, false);
     return ok;
 }
 
@@ -2081,7 +2098,7 @@ bool plh_stage_output(struct frame_job *job)
         int dithered = 0;
         switch (rp_pick_dither(&job->caps, params, out.dither_depth, ph)) {
         case RP_DITHER_ERROR_DIFFUSION:
-            if (run_error_diffusion(job, &sh, out.dither_depth, plane->components, pw, ph)) {
+            if (run_error_diffusion(job, &sh, out.dither_depth, plane, pw, ph)) {
                 dithered = out.dither_depth;
                 break;
             }

@@ -389,3 +389,75 @@ def test_repeat_and_mirror_equal_clamped_sampling_of_the_periods_written_out(rec
         a = orc.sample_polar(img, w, radius, rz, 64, 32, rect=rect, address_mode=mode, gather_order=gather)
         b = orc.sample_polar(big, w, radius, rz, 64, 32, rect=shifted(rect), gather_order=gather)
         assert np.array_equal(a, b), (gather, float(np.abs(a - b).max()))
+
+
+# ---- error diffusion (src/shaders/dithering.c:326-527) in raster order ------------------------
+
+ED_KERNELS = ["simple", "false-fs", "sierra-lite", "floyd-steinberg", "atkinson",
+              "jarvis-judice-ninke", "stucki", "burkes", "sierra-2", "sierra-3"]
+ED_SIZES = [(1, 1), (1, 7), (2, 3), (3, 1), (5, 4), (33, 17), (17, 40)]      # width, height
+
+
+def error_diffusion_table():
+    """{name: (shift, divisor, pattern)} from pl_error_diffusion_kernels of the built library
+    (test_tier0_ref.py pins that table to the reference's)"""
+    import libplacebo_amd as pl
+    from libplacebo_amd import _capi as capi
+    n = C.c_int.in_dll(pl.lib(), "pl_num_error_diffusion_kernels").value
+    arr = (C.POINTER(capi.ErrorDiffusionKernel) * (n + 1)).in_dll(pl.lib(), "pl_error_diffusion_kernels")
+    assert not arr[n]
+    return {arr[i].contents.name.decode(): (arr[i].contents.shift, arr[i].contents.divisor,
+                                            [list(row) for row in arr[i].contents.pattern])
+            for i in range(n)}
+
+
+def diffuse_in_raster_order(img, depth, divisor, pattern):
+    """What the shader computes, without its schedule: no shear, no ring buffer, no packed word.
+    Pixels are visited row by row, left to right -- a valid order, since every weight of a pattern
+    points right on the same row or to a later row, so a pixel has received all of its error by
+    the time it is visited. `received` is one integer plane per channel, padded by the pattern's
+    reach (two columns on each side, two rows below); what falls into the padding on the right and
+    below is never read, and a contribution that would leave through the left border is not made
+    ("if (x >= -dx)", :508-514). The sum a pixel has received is folded to a signed 8-bit value
+    when it is read: the shader adds the weights as bytes of one word, each channel wrapping on its
+    own (that is what the word's padding is for, :445-462), and reads `((word + bias) >> s) & 0xFF)
+    - 128`. The float steps are the shader's, one float32 operation each, round() as half-to-even."""
+    f = np.float32
+    h, w = img.shape[:2]
+    quant = f((1 << depth) - 1)
+    received = np.zeros((h + 2, w + 4, 3), np.int64)
+    taps = [(dx, dy, pattern[dy][dx + 2]) for dy in range(3) for dx in range(-2, 3) if pattern[dy][dx + 2]]
+    out = img.copy()                                                # alpha: pix_orig.a
+    for y in range(h):
+        for x in range(w):
+            e = ((received[y, x + 2] + 128) & 0xFF) - 128
+            pix = img[y, x, :3] * quant + e.astype(f) / f(254)
+            dithered = np.rint(pix)
+            out[y, x, :3] = dithered / quant
+            err_divided = (pix - dithered) * f(254) / f(divisor)
+            for dx, dy, k in taps:
+                if x + dx >= 0:
+                    received[y + dy, x + dx + 2] += np.rint(err_divided * f(k)).astype(np.int64)
+    assert out.dtype == np.float32
+    return out
+
+
+@pytest.mark.parametrize("name", ED_KERNELS)
+def test_error_diffusion_against_a_raster_scan_restatement(name):
+    """orc_error_diffusion is the kernel's algorithm run sequentially: the same shear, the same ring
+    indexing, the same packed word. A misreading of any of them would be shared. The restatement
+    above shares none of them, and must give the same words."""
+    table = error_diffusion_table()
+    assert sorted(table) == sorted(ED_KERNELS)
+    shift, divisor, pattern = table[name]
+    rng = np.random.default_rng(ED_KERNELS.index(name))
+    cases = [(w, h, depth, 0.0, 1.0) for (w, h) in ED_SIZES for depth in (1, 4, 10)]
+    cases.append((33, 17, 8, -0.25, 1.5))           # nothing clamps: the error stays within half a step
+    for w, h, depth, lo, hi in cases:
+        img = (lo + (hi - lo) * rng.random((h, w, 4))).astype(np.float32)
+        got = orc.error_diffusion(img, depth, shift, divisor, pattern)
+        want = diffuse_in_raster_order(img, depth, divisor, pattern)
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), \
+            (w, h, depth, int((got.view(np.uint32) != want.view(np.uint32)).sum()))
+        if lo < 0:
+            assert got[..., :3].min() < 0 and got[..., :3].max() > 1
