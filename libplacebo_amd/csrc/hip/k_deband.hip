@@ -31,6 +31,7 @@
 #include "prng.hiph"
 #include "samplers.hiph"
 #include "backend.h"
+#include "launch_ladder.hiph"
 
 #define DEBAND_BW 64
 #define DEBAND_BH 4
@@ -575,8 +576,10 @@ static bool deband_fast_ops(const plh_pass *pass)
     return i == pass->num_ops;
 }
 
+/* ---- the candidates for a debanding pass (launch_ladder.hiph), in the order of plh_launch_deband's table ---- */
+
 // the shape k_deband_fast is written for
-static bool deband_fast_applies(const plh_pass *pass)
+static bool deband_fast_applies(plh_pass *pass)
 {
     const plh_sampler_args &s = pass->s;
     if (!plh_switch(PLH_SW_DEBAND_FAST))
@@ -588,42 +591,63 @@ static bool deband_fast_applies(const plh_pass *pass)
            !pass->num_pre_ops && deband_fast_ops(pass);
 }
 
-int plh_launch_deband(hipStream_t stream, const plh_pass *pass)
+static int launch_deband_fast(hipStream_t stream, const plh_pass *pass)
 {
-    if (deband_fast_applies(pass)) {
-        const plh_sampler_args &s = pass->s;
-        if (plh_switch(PLH_SW_DEBAND_LDS) && s.db_lds && s.iterations >= 1 && s.db_radius * (float) s.iterations <= 16.0f) {
-            plh_trace_kernel("k_deband_lds");
-            int cus = 256;
-            (void) plh_stream_device((plh_stream) stream, &cus);
-            const int tiles_x = (pass->width + DBL_TW - 1) / DBL_TW;
-            // (8 bands of tile columns, padded to the widest: k_deband_lds)
-#define DBL_LAUNCH(TH) do { \
-                const size_t shmem = (size_t) DBL_WW * (TH + 2 * DBL_HALO) * 8; \
-                const int tiles_y = (pass->height + TH - 1) / TH; \
-                const dim3 grid(8 * ((tiles_x + 7) / 8) * tiles_y); \
-                return plh_launch_last_lds<k_deband_lds<TH>>(grid, dim3(DBL_NT), shmem, stream, *pass); \
-            } while (0)
-            // fewer than two rounds of 32-row tiles (three workgroups per CU): 16-row tiles
-            if (tiles_x * ((pass->height + 31) / 32) < 2 * 3 * cus)
-                DBL_LAUNCH(16);
-            DBL_LAUNCH(32);
-#undef DBL_LAUNCH
-        }
-        const int nbx = (pass->width + 2 * DBF_BW - 1) / (2 * DBF_BW);
-        const int nby = (pass->height + DBF_BH - 1) / DBF_BH;
-        const dim3 grid(nbx, nby);
-        plh_trace_kernel("k_deband_fast");
-        PLH_LAUNCH_LAST(k_deband_fast, grid, dim3(DBF_BW, DBF_BH), 0, stream, *pass);
-        return plh_launch_status();
-    }
+    const int nbx = (pass->width + 2 * DBF_BW - 1) / (2 * DBF_BW);
+    const int nby = (pass->height + DBF_BH - 1) / DBF_BH;
+    PLH_LAUNCH_LAST(k_deband_fast, dim3(nbx, nby), dim3(DBF_BW, DBF_BH), 0, stream, *pass);
+    return plh_launch_status();
+}
+
+// k_deband_lds: the same shape where the window it stages holds every tap (the host says whether
+// the LDS limit allows that window: db_lds)
+static bool deband_lds_applies(plh_pass *pass)
+{
+    const plh_sampler_args &s = pass->s;
+    return deband_fast_applies(pass) && plh_switch(PLH_SW_DEBAND_LDS) && s.db_lds && s.iterations >= 1 &&
+           s.db_radius * (float) s.iterations <= 16.0f;
+}
+
+// tiles of TH rows, in 8 bands of tile columns, padded to the widest (k_deband_lds)
+template <int TH>
+static int launch_deband_lds_rows(hipStream_t stream, const plh_pass *pass)
+{
+    const int tiles_x = (pass->width + DBL_TW - 1) / DBL_TW, tiles_y = (pass->height + TH - 1) / TH;
+    const size_t shmem = (size_t) DBL_WW * (TH + 2 * DBL_HALO) * 8;
+    const dim3 grid(8 * ((tiles_x + 7) / 8) * tiles_y);
+    return plh_launch_last_lds<k_deband_lds<TH>>(grid, dim3(DBL_NT), shmem, stream, *pass);
+}
+
+static int launch_deband_lds(hipStream_t stream, const plh_pass *pass)
+{
+    int cus = 256;
+    (void) plh_stream_device((plh_stream) stream, &cus);
+    const int tiles_x = (pass->width + DBL_TW - 1) / DBL_TW;
+    // fewer than two rounds of 32-row tiles (three workgroups per CU): 16-row tiles
+    if (tiles_x * ((pass->height + 31) / 32) < 2 * 3 * cus)
+        return launch_deband_lds_rows<16>(stream, pass);
+    return launch_deband_lds_rows<32>(stream, pass);
+}
+
+// k_deband: every debanding pass
+static int launch_deband(hipStream_t stream, const plh_pass *pass)
+{
     const dim3 block(DEBAND_BW, DEBAND_BH);
     const dim3 grid((pass->width + DEBAND_BW - 1) / DEBAND_BW,
                     (pass->height + DEBAND_BH - 1) / DEBAND_BH);
-    plh_trace_kernel("k_deband");
     if (plh_ops_lite(pass, 0, pass->num_ops))
         PLH_LAUNCH_LAST(k_deband<true>, grid, block, 0, stream, *pass);
     else
         PLH_LAUNCH_LAST(k_deband<false>, grid, block, 0, stream, *pass);
     return plh_launch_status();
+}
+
+int plh_launch_deband(hipStream_t stream, const plh_pass *pass)
+{
+    static const plh_candidate candidates[] = {
+        { "k_deband_lds",  deband_lds_applies,  launch_deband_lds },    // the taps' window staged in LDS
+        { "k_deband_fast", deband_fast_applies, launch_deband_fast },   // the same pass, taps fetched from memory
+        { "k_deband",      plh_applies_always,  launch_deband },        // every pass
+    };
+    return plh_launch_first(candidates, stream, pass);
 }

@@ -18,6 +18,7 @@
 
 #include "colorops.hiph"
 #include "backend.h"
+#include "launch_ladder.hiph"
 
 #define DEINT_BW 64
 #define DEINT_BH 4
@@ -508,65 +509,113 @@ void k_deint_rows_yadif(const plh_pass p_)
     put(yr, 0, out, false);
 }
 
-// whether the pass is what k_deint_rows does: a whole unorm plane into a texture of its own
-// format, or of floats with the same components, every row a whole number of dwords
-static int deint_rows_variant(const plh_pass *p)
+/* ---- the candidates for a deinterlacing pass (launch_ladder.hiph), in the order of plh_launch_deinterlace's table ---- */
+
+// What the row-wise kernels (k_deint_rows, k_deint_rows_yadif) do: a whole unorm plane into a
+// texture of its own format, or of floats with the same components, every row a whole number of dwords.
+struct deint_rows_plan {
+    bool rows;      // the pass is such a pass
+    bool wide;      // 16-bit elements (else 8-bit ones)
+    bool f32;       // into the float target
+    int nc;         // components per texel
+};
+
+static deint_rows_plan deint_rows_plan_of(const plh_pass *p)
 {
     const plh_view &s = p->s.src, &d = p->dst;
     const plh_deint_args &a = p->deint;
+    const deint_rows_plan none = {};
     if (p->num_ops || a.keep < 0 || s.fmt > PLH_FMT_RGBA16)
-        return 0;
+        return none;
     if (a.algo == PLH_DEINT_YADIF && s.fmt > PLH_FMT_RG16)
-        return 0;   // (rgba16: a window of 13 dwords per row for half a pixel: the general kernel)
+        return none;    // (rgba16: a window of 13 dwords per row for half a pixel: the general kernel)
     const int nc = (s.fmt - 1) % 3 == 2 ? 4 : (s.fmt - 1) % 3 + 1;
     const bool same = d.fmt == s.fmt, f32 = d.fmt == PLH_FMT_R32F + (s.fmt - 1) % 3;
     if ((!same && !f32) || p->s.comp_mask != (1u << nc) - 1u)
-        return 0;
+        return none;
     if (p->base_x || p->base_y || p->dir_x != 1 || p->dir_y != 1 || p->transpose ||
         p->width != s.w || p->height != s.h || d.w != s.w || d.h != s.h)
-        return 0;
+        return none;
     const plh_view *views[3] = { &s, &a.prev, &a.next };
     for (const plh_view *v : views) {
         if (v->fmt != s.fmt || v->w != s.w || v->h != s.h || v->pitch % 4 || (uintptr_t) v->ptr % 4)
-            return 0;
+            return none;
     }
     if (d.pitch % 4 || (uintptr_t) d.ptr % 4)
-        return 0;
-    return (s.fmt <= PLH_FMT_RGBA8 ? 1 : 2) + (f32 ? 2 : 0);
+        return none;
+    return { true, s.fmt > PLH_FMT_RGBA8, f32, nc };
 }
 
-extern "C" int plh_launch_deinterlace(plh_stream stream_, const struct plh_pass *pass)
+static dim3 deint_block() { return dim3(DEINT_BW * DEINT_BH); }
+
+// a lane per dword of a source row, a row of the workgroup per row pair
+static dim3 deint_rows_grid(const plh_pass *pass, const deint_rows_plan &plan)
 {
-    hipStream_t stream = (hipStream_t) stream_;
     const int pairs = (pass->height + 1) / 2;
-    const dim3 block(DEINT_BW * DEINT_BH);
-    if (const int variant = deint_rows_variant(pass)) {
-        const int nc = (pass->s.src.fmt - 1) % 3 == 2 ? 4 : (pass->s.src.fmt - 1) % 3 + 1;
-        const int dwords = (pass->s.src.w * nc * (variant & 1 ? 1 : 2) + 3) / 4;
-        const dim3 grid((dwords + DEINT_BW - 1) / DEINT_BW, (pairs + DEINT_BH - 1) / DEINT_BH);
-        if (pass->deint.algo == PLH_DEINT_YADIF) {
-#define YADIF(C, NC) do { \
-                if (variant > 2) PLH_LAUNCH_LAST((k_deint_rows_yadif<C, NC, true>), grid, block, 0, stream, *pass); \
-                else PLH_LAUNCH_LAST((k_deint_rows_yadif<C, NC, false>), grid, block, 0, stream, *pass); \
-            } while (0)
-            if (variant & 1) {
-                if (nc == 1) YADIF(uint8_t, 1); else if (nc == 2) YADIF(uint8_t, 2); else YADIF(uint8_t, 4);
-            } else {
-                if (nc == 1) YADIF(uint16_t, 1); else YADIF(uint16_t, 2);
-            }
-#undef YADIF
-        } else switch (variant) {
-        case 1: PLH_LAUNCH_LAST((k_deint_rows<uint8_t, false>), grid, block, 0, stream, *pass); break;
-        case 2: PLH_LAUNCH_LAST((k_deint_rows<uint16_t, false>), grid, block, 0, stream, *pass); break;
-        case 3: PLH_LAUNCH_LAST((k_deint_rows<uint8_t, true>), grid, block, 0, stream, *pass); break;
-        default: PLH_LAUNCH_LAST((k_deint_rows<uint16_t, true>), grid, block, 0, stream, *pass); break;
-        }
-        return plh_launch_status();
+    const int dwords = (pass->s.src.w * plan.nc * (plan.wide ? 2 : 1) + 3) / 4;
+    return dim3((dwords + DEINT_BW - 1) / DEINT_BW, (pairs + DEINT_BH - 1) / DEINT_BH);
+}
+
+static bool deint_rows_yadif_applies(plh_pass *pass)
+{
+    return pass->deint.algo == PLH_DEINT_YADIF && deint_rows_plan_of(pass).rows;
+}
+
+// k_deint_rows_yadif's instance: 8-bit elements of 1, 2 or 4 components, 16-bit ones of 1 or 2
+static plh_pass_launch_fn *deint_rows_yadif_instance(const deint_rows_plan &plan)
+{
+#define YADIF(C, NC) return plan.f32 ? plh_launch_last_lds<k_deint_rows_yadif<C, NC, true>> \
+                                     : plh_launch_last_lds<k_deint_rows_yadif<C, NC, false>>
+    if (!plan.wide) {
+        if (plan.nc == 1) YADIF(uint8_t, 1);
+        if (plan.nc == 2) YADIF(uint8_t, 2);
+        YADIF(uint8_t, 4);
     }
+    if (plan.nc == 1) YADIF(uint16_t, 1);
+    YADIF(uint16_t, 2);
+#undef YADIF
+}
+
+static int launch_deint_rows_yadif(hipStream_t stream, const plh_pass *pass)
+{
+    const deint_rows_plan plan = deint_rows_plan_of(pass);
+    return deint_rows_yadif_instance(plan)(deint_rows_grid(pass, plan), deint_block(), 0, stream, *pass);
+}
+
+static bool deint_rows_applies(plh_pass *pass)
+{
+    return pass->deint.algo != PLH_DEINT_YADIF && deint_rows_plan_of(pass).rows;
+}
+
+static int launch_deint_rows(hipStream_t stream, const plh_pass *pass)
+{
+    const deint_rows_plan plan = deint_rows_plan_of(pass);
+    const dim3 grid = deint_rows_grid(pass, plan), block = deint_block();
+    if (!plan.wide && !plan.f32)    PLH_LAUNCH_LAST((k_deint_rows<uint8_t, false>), grid, block, 0, stream, *pass);
+    else if (!plan.f32)             PLH_LAUNCH_LAST((k_deint_rows<uint16_t, false>), grid, block, 0, stream, *pass);
+    else if (!plan.wide)            PLH_LAUNCH_LAST((k_deint_rows<uint8_t, true>), grid, block, 0, stream, *pass);
+    else                            PLH_LAUNCH_LAST((k_deint_rows<uint16_t, true>), grid, block, 0, stream, *pass);
+    return plh_launch_status();
+}
+
+// k_deinterlace: every deinterlacing pass
+static int launch_deinterlace(hipStream_t stream, const plh_pass *pass)
+{
+    const int pairs = (pass->height + 1) / 2;
     const dim3 grid((pass->width + DEINT_BW - 1) / DEINT_BW, (pairs + DEINT_BH - 1) / DEINT_BH);
     if (plh_ops_lite(pass, 0, pass->num_ops))
-        PLH_LAUNCH_LAST(k_deinterlace<true>, grid, block, 0, stream, *pass);
+        PLH_LAUNCH_LAST(k_deinterlace<true>, grid, deint_block(), 0, stream, *pass);
     else
-        PLH_LAUNCH_LAST(k_deinterlace<false>, grid, block, 0, stream, *pass);
+        PLH_LAUNCH_LAST(k_deinterlace<false>, grid, deint_block(), 0, stream, *pass);
     return plh_launch_status();
+}
+
+extern "C" int plh_launch_deinterlace(plh_stream stream, const struct plh_pass *pass)
+{
+    static const plh_candidate candidates[] = {
+        { "k_deint_rows_yadif", deint_rows_yadif_applies, launch_deint_rows_yadif },    // unorm planes, row-wise: yadif
+        { "k_deint_rows",       deint_rows_applies,       launch_deint_rows },          // ... weave, bob, bwdif
+        { "k_deinterlace",      plh_applies_always,       launch_deinterlace },         // every pass
+    };
+    return plh_launch_first(candidates, (hipStream_t) stream, pass);
 }

@@ -23,6 +23,7 @@
 #include "colorops.hiph"
 #include "samplers.hiph"
 #include "fastepi.hiph"
+#include "launch_ladder.hiph"
 
 #define ORTHO_BW 64
 #define ORTHO_BH 4
@@ -528,62 +529,7 @@ void k_ortho_fast(const plh_pass p_)
     }
 }
 
-template <int SRC>
-static void launch_ortho_fast(hipStream_t stream, const plh_pass *pass, int epi)
-{
-    const dim3 block(ORTHO_BW, ORTHO_BH);
-    const dim3 grid(((pass->width + 1) / 2 + ORTHO_BW - 1) / ORTHO_BW,
-                    (pass->height + ORTHO_BH - 1) / ORTHO_BH);
-#define LAUNCH_N(E, NT) do { \
-        if (pass->s.dir) PLH_LAUNCH_LAST((k_ortho_fast<SRC, E, 1, NT>), grid, block, 0, stream, *pass); \
-        else             PLH_LAUNCH_LAST((k_ortho_fast<SRC, E, 0, NT>), grid, block, 0, stream, *pass); \
-    } while (0)
-    // (the variants with the tap count at compile time stage the weight table in LDS and take its
-    // row pitch from the tap count: rows padded to a multiple of four floats, as the host makes them)
-    const bool packed_rows = pass->s.row_stride == (pass->s.row_size + 3) / 4 * 4;
-#define LAUNCH(E) do { \
-        if (pass->s.row_size == 4 && packed_rows)      LAUNCH_N(E, 4); \
-        else if (pass->s.row_size == 6 && packed_rows) LAUNCH_N(E, 6); \
-        else if (pass->s.row_size == 8 && packed_rows) LAUNCH_N(E, 8); \
-        else                                           LAUNCH_N(E, 16); \
-    } while (0)
-    if (pass->s.use_linear) {
-        // linear-trick filters (bicubic / gaussian / hermite ... low-pass), any tap count; colour
-        // ops behind them only as the fused epilogue / the map chain, packed sources
-        // (the tap count at compile time where it is 4 or 8 -- a halving with hermite / bicubic: the
-        // run-time form issues all 16 loads whatever the count)
-#define LAUNCH_LIN_N(E, NT) do { \
-            if (pass->s.dir) PLH_LAUNCH_LAST((k_ortho_fast<SRC, E, 1, NT, true>), grid, block, 0, stream, *pass); \
-            else             PLH_LAUNCH_LAST((k_ortho_fast<SRC, E, 0, NT, true>), grid, block, 0, stream, *pass); \
-        } while (0)
-#define LAUNCH_LIN(E) do { \
-            if (pass->s.row_size == 4 && packed_rows)      LAUNCH_LIN_N(E, 4); \
-            else if (pass->s.row_size == 8 && packed_rows) LAUNCH_LIN_N(E, 8); \
-            else                                           LAUNCH_LIN_N(E, 16); \
-        } while (0)
-        if constexpr (SRC == PLH_FMT_RGBA16 || SRC == PLH_FMT_RGBA16F) {
-            if (epi == 1)      LAUNCH_LIN(1);
-            else if (epi == 4) LAUNCH_LIN(4);
-            else               LAUNCH_LIN(0);
-        } else {
-            LAUNCH_LIN(0);
-        }
-#undef LAUNCH_LIN
-#undef LAUNCH_LIN_N
-        return;
-    }
-    if constexpr (SRC == PLH_FMT_RGBA16 || SRC == PLH_FMT_RGBA16F) {
-        if (epi == 0)      LAUNCH(0);
-        else if (epi == 1) LAUNCH(1);
-        else if (epi == 2) LAUNCH(2);
-        else if (epi == 4) LAUNCH(4);
-        else               LAUNCH(3);
-    } else {
-        LAUNCH(0);      // plane passes: no colour ops (ortho_fast_variant)
-    }
-#undef LAUNCH
-#undef LAUNCH_N
-}
+/* ---- the candidates for a separable pass (launch_ladder.hiph), in the order of plh_launch_ortho's table ---- */
 
 static bool ortho_fast_packed(int fmt)
 {
@@ -596,10 +542,82 @@ static bool ortho_fast_plane(int fmt)
            fmt == PLH_FMT_R16F || fmt == PLH_FMT_RG16F;
 }
 
-// -1: not eligible, else the epilogue variant
-static int ortho_fast_variant(plh_pass *pass)
+// k_ortho_fast's epilogue variant, of a pass whose copy the matchers have run into
+// (ortho_fast_applies): 0 no colour ops, 1 the fused epilogue, 4 the map chain, 2 / 3 the
+// interpreter without / with transcendentals
+static int ortho_fast_epilogue(const plh_pass *pass)
 {
-    const int enabled = plh_switch(PLH_SW_ORTHO_FAST);
+    if (!pass->num_ops)
+        return 0;
+    if (pass->chain.enabled)    // (first: a chain that matched has left its tail in pass->epi)
+        return 4;
+    if (pass->epi.enabled)
+        return 1;
+    return plh_ops_lite(pass, 0, pass->num_ops) ? 2 : 3;
+}
+
+// ... and for that variant E, LIN (linear-trick weight rows) and texels SRC: the instance for the
+// pass's direction and tap count
+template <int SRC, int E, bool LIN>
+static plh_pass_launch_fn *ortho_fast_taps(const plh_pass *pass)
+{
+    const plh_sampler_args &s = pass->s;
+#define TAPS(NT) return s.dir ? plh_launch_last_lds<k_ortho_fast<SRC, E, 1, NT, LIN>> \
+                              : plh_launch_last_lds<k_ortho_fast<SRC, E, 0, NT, LIN>>
+    // (the variants with the tap count at compile time stage the weight table in LDS and take its
+    // row pitch from the tap count: rows padded to a multiple of four floats, as the host makes them.
+    // LIN has them where the count is 4 or 8 -- a halving with hermite / bicubic -- and not for 6)
+    if (s.row_stride == (s.row_size + 3) / 4 * 4) {
+        switch (s.row_size) {
+        case 4: TAPS(4);
+        case 6: if constexpr (!LIN) TAPS(6); else break;
+        case 8: TAPS(8);
+        }
+    }
+    TAPS(16);   // the tap count at run time: every count ortho_fast_applies lets through
+#undef TAPS
+}
+
+// k_ortho_fast's instance for the pass, NULL: there is none. Planes (one or two components) have
+// the variant without colour ops; the LIN form has the interpreter's variants for no source.
+template <int SRC>
+static plh_pass_launch_fn *ortho_fast_variants(const plh_pass *pass)
+{
+    const int epi = ortho_fast_epilogue(pass);
+    if (pass->s.use_linear) {
+        if constexpr (SRC == PLH_FMT_RGBA16 || SRC == PLH_FMT_RGBA16F) {
+            if (epi == 1) return ortho_fast_taps<SRC, 1, true>(pass);
+            if (epi == 4) return ortho_fast_taps<SRC, 4, true>(pass);
+        }
+        return epi == 0 ? ortho_fast_taps<SRC, 0, true>(pass) : NULL;
+    }
+    if (epi == 0) return ortho_fast_taps<SRC, 0, false>(pass);
+    if constexpr (SRC == PLH_FMT_RGBA16 || SRC == PLH_FMT_RGBA16F) {
+        if (epi == 1) return ortho_fast_taps<SRC, 1, false>(pass);
+        if (epi == 2) return ortho_fast_taps<SRC, 2, false>(pass);
+        if (epi == 4) return ortho_fast_taps<SRC, 4, false>(pass);
+        if (epi == 3) return ortho_fast_taps<SRC, 3, false>(pass);
+    }
+    return NULL;
+}
+
+static plh_pass_launch_fn *ortho_fast_instance(const plh_pass *pass)
+{
+    switch (pass->s.src.fmt) {
+    case PLH_FMT_RGBA16F: return ortho_fast_variants<PLH_FMT_RGBA16F>(pass);
+    case PLH_FMT_RGBA16:  return ortho_fast_variants<PLH_FMT_RGBA16>(pass);
+    case PLH_FMT_R8:      return ortho_fast_variants<PLH_FMT_R8>(pass);
+    case PLH_FMT_RG8:     return ortho_fast_variants<PLH_FMT_RG8>(pass);
+    case PLH_FMT_R16:     return ortho_fast_variants<PLH_FMT_R16>(pass);
+    case PLH_FMT_RG16:    return ortho_fast_variants<PLH_FMT_RG16>(pass);
+    case PLH_FMT_R16F:    return ortho_fast_variants<PLH_FMT_R16F>(pass);
+    case PLH_FMT_RG16F:   return ortho_fast_variants<PLH_FMT_RG16F>(pass);
+    default:              return NULL;
+    }
+}
+
+static bool ortho_fast_applies(plh_pass *pass)
+{
     const plh_sampler_args &s = pass->s;
     const int n_axis = s.dir ? s.src.h : s.src.w;
     const int n_across = s.dir ? s.src.w : s.src.h;
@@ -607,77 +625,60 @@ static int ortho_fast_variant(plh_pass *pass)
     const bool addr_ok = s.address_mode == PLH_ADDRESS_CLAMP ||
                          (s.address_mode == PLH_ADDRESS_MIRROR &&
                           plh_ortho_one_reflection(n_axis, n_across, s.row_size, s.pos, s.dir));
-    if (s.use_linear) {
-        // the LIN variant: run-time tap count (even, <= 16); no colour ops, or -- packed sources:
-        // the last pass of a downscale in linear light, pl_render_default_params 4K -> 1080p -- the
-        // fused epilogue / the map chain (DELINEARIZE + dither) behind it
-        if (!enabled || !addr_ok || s.linear || (s.row_size & 1) || s.row_size < 2 ||
-            s.row_size > 16 || (s.row_stride & 3) || pass->num_pre_ops ||
-            (!ortho_fast_packed(s.src.fmt) && !ortho_fast_plane(s.src.fmt)))
-            return -1;
-        if (!pass->num_ops)
-            return 0;
+    // the tap count: even, up to 16 -- the LIN form (linear-trick filters: bicubic / gaussian /
+    // hermite ... low-pass) from 2, the plain one from 4 (below 10 a compile-time count, above the
+    // run-time form of the widened, anti-aliased kernels)
+    const bool taps_ok = !(s.row_size & 1) && s.row_size >= (s.use_linear ? 2 : 4) && s.row_size <= 16;
+    if (!plh_switch(PLH_SW_ORTHO_FAST) || !addr_ok || s.linear || !taps_ok || (s.row_stride & 3) ||
+        pass->num_pre_ops)
+        return false;
+    // Colour ops behind a packed source only (planes with them: the generic kernel). As the fused
+    // epilogue or the map chain (the last pass of a downscale in linear light,
+    // pl_render_default_params 4K -> 1080p: DELINEARIZE + dither) for either form; the plain form
+    // also through the interpreter, bar the ops that need their own kernels
+    if (pass->num_ops) {
         if (!ortho_fast_packed(s.src.fmt))
-            return -1;
+            return false;
         plh_match_fast_epilogue(pass, true);
         if (pass->epi.enabled)
-            return 1;
-        plh_match_map_chain(pass);
-        return pass->chain.enabled ? 4 : -1;
+            pass->chain = plh_map_chain{};  // (not asked for: ortho_fast_epilogue looks at both)
+        else
+            plh_match_map_chain(pass);
+        if (!pass->epi.enabled && !pass->chain.enabled &&
+            (plh_pass_has_op(pass, PLH_OP_PEAK_DETECT) || plh_pass_has_op(pass, PLH_OP_MIX_ADD)))
+            return false;
     }
-    if (!enabled || !addr_ok || s.linear ||
-        (s.row_size != 4 && s.row_size != 6 && s.row_size != 8 &&
-         !(s.row_size >= 10 && s.row_size <= 16 && !(s.row_size & 1))) ||
-        (s.row_stride & 3) || pass->num_pre_ops ||
-        (!ortho_fast_packed(s.src.fmt) && !ortho_fast_plane(s.src.fmt)))
-        return -1;
-    if (!pass->num_ops)
-        return 0;
-    if (!ortho_fast_packed(s.src.fmt))
-        return -1;  // planes with colour ops: generic kernel
-    plh_match_fast_epilogue(pass, true);
-    if (pass->epi.enabled)
-        return 1;
-    plh_match_map_chain(pass);
-    if (pass->chain.enabled)
-        return 4;
-    for (int i = 0; i < pass->num_ops; i++) {
-        const int k = pass->ops[i].kind;
-        if (k == PLH_OP_PEAK_DETECT || k == PLH_OP_MIX_ADD)
-            return -1;  // need their own kernels
-    }
-    return plh_ops_lite(pass, 0, pass->num_ops) ? 2 : 3;
+    return ortho_fast_instance(pass) != NULL;
 }
 
-int plh_launch_ortho(hipStream_t stream, const plh_pass *pass)
+static int launch_ortho_fast(hipStream_t stream, const plh_pass *pass)
 {
-    {
-        plh_pass local = *pass;
-        const int epi = ortho_fast_variant(&local);
-        if (epi >= 0) {
-            plh_trace_kernel("k_ortho_fast");
-            switch (local.s.src.fmt) {
-            case PLH_FMT_RGBA16F: launch_ortho_fast<PLH_FMT_RGBA16F>(stream, &local, epi); break;
-            case PLH_FMT_RGBA16:  launch_ortho_fast<PLH_FMT_RGBA16>(stream, &local, epi); break;
-            case PLH_FMT_R8:      launch_ortho_fast<PLH_FMT_R8>(stream, &local, epi); break;
-            case PLH_FMT_RG8:     launch_ortho_fast<PLH_FMT_RG8>(stream, &local, epi); break;
-            case PLH_FMT_R16:     launch_ortho_fast<PLH_FMT_R16>(stream, &local, epi); break;
-            case PLH_FMT_RG16:    launch_ortho_fast<PLH_FMT_RG16>(stream, &local, epi); break;
-            case PLH_FMT_R16F:    launch_ortho_fast<PLH_FMT_R16F>(stream, &local, epi); break;
-            default:              launch_ortho_fast<PLH_FMT_RG16F>(stream, &local, epi); break;
-            }
-            return plh_launch_status();
-        }
-    }
+    const dim3 block(ORTHO_BW, ORTHO_BH);
+    const dim3 grid(((pass->width + 1) / 2 + ORTHO_BW - 1) / ORTHO_BW,
+                    (pass->height + ORTHO_BH - 1) / ORTHO_BH);
+    return ortho_fast_instance(pass)(grid, block, 0, stream, *pass);
+}
+
+// k_ortho: every separable pass
+static int launch_ortho(hipStream_t stream, const plh_pass *pass)
+{
     const dim3 block(ORTHO_BW, ORTHO_BH);
     const dim3 grid((pass->width + ORTHO_BW - 1) / ORTHO_BW,
                     (pass->height + ORTHO_BH - 1) / ORTHO_BH);
-    plh_trace_kernel("k_ortho");
     if (plh_ops_lite(pass, 0, pass->num_ops))
         PLH_LAUNCH_LAST(k_ortho<true>, grid, block, 0, stream, *pass);
     else
         PLH_LAUNCH_LAST(k_ortho<false>, grid, block, 0, stream, *pass);
     return plh_launch_status();
+}
+
+int plh_launch_ortho(hipStream_t stream, const plh_pass *pass)
+{
+    static const plh_candidate candidates[] = {
+        { "k_ortho_fast", ortho_fast_applies, launch_ortho_fast },  // two pixels per lane, the taps unrolled
+        { "k_ortho",      plh_applies_always, launch_ortho },       // every pass
+    };
+    return plh_launch_first(candidates, stream, pass);
 }
 
 

@@ -16,6 +16,7 @@
 #include "backend.h"
 #include "samplers.hiph"
 #include "fastepi.hiph"
+#include "launch_ladder.hiph"
 
 #include "k_pass_generic.hiph"
 
@@ -659,29 +660,40 @@ void k_pass_merge(const plh_pass p_, const plh_merge m)
     }
 }
 
-// Is this the merge pass k_pass_merge is written for? Fills `m`, pass->chain and pass->epi.
-static bool pass_merge_applies(plh_pass *pass, plh_merge *m)
+// The head of the merge pass k_pass_merge is written for, as `m`: the index of the first op behind
+// it, or -1 where the pass is none (k_pass_merge's plan: its test and its launch both ask here)
+static int pass_merge_plan(const plh_pass *pass, plh_merge *m)
 {
     const plh_sampler_args &s = pass->s;
     if (!plh_switch(PLH_SW_PASS_NATIVE))
-        return false;
+        return -1;
     if (!plh_pass_covers_source(pass) || s.type != PLH_SAMPLE_NEAREST ||
         s.address_mode != PLH_ADDRESS_CLAMP || pass->transpose || pass->num_pre_ops ||
         !plh_pass_plain_target(pass) ||
         (pass->dst.fmt != PLH_FMT_RGBA16 && pass->dst.fmt != PLH_FMT_RGBA16F))
-        return false;
+        return -1;
     const int n = pass->num_ops;
     int i = 0;
     *m = plh_merge{ -1, -1, -1, -1 };
     if (i < n && pass->ops[i].kind == PLH_OP_PLANE_MAP)
         m->pmap = i++;
     if (!(i < n && pass->ops[i].kind == PLH_OP_PLANE_FETCH))
-        return false;
+        return -1;
     m->fetch0 = i++;
     if (i < n && pass->ops[i].kind == PLH_OP_PLANE_FETCH)
         m->fetch1 = i++;
     if (i < n && pass->ops[i].kind == PLH_OP_AFFINE)
         m->affine = i++;
+    return i;
+}
+
+// Is this the merge pass k_pass_merge is written for? Fills pass->chain and pass->epi.
+static bool pass_merge_applies(plh_pass *pass)
+{
+    plh_merge m;
+    const int i = pass_merge_plan(pass, &m), n = pass->num_ops;
+    if (i < 0)
+        return false;
     pass->chain = plh_map_chain{ 0, -1, -1, -1, -1, -1, -1, 0, -1, -1, -1, 0 };
     pass->epi = plh_fast_epi{};
     if (i == n)
@@ -798,35 +810,36 @@ void k_pass_mix(const plh_pass p_, const plh_mixplan m)
     }
 }
 
-// Is this the blending pass k_pass_mix is written for? Fills `m` and pass->epi.
-static bool pass_mix_applies(plh_pass *pass, plh_mixplan *m)
+// The blending pass k_pass_mix is written for, as `m`: the index of the first op behind the blend,
+// or -1 where the pass is none (k_pass_mix's plan: its test and its launch both ask here)
+static int pass_mix_plan(const plh_pass *pass, plh_mixplan *m)
 {
     const plh_sampler_args &s = pass->s;
     if (!plh_switch(PLH_SW_PASS_NATIVE))
-        return false;
+        return -1;
     if (!plh_pass_covers_source(pass) || s.type != PLH_SAMPLE_NEAREST ||
         s.address_mode != PLH_ADDRESS_CLAMP || pass->transpose || pass->num_pre_ops ||
         !plh_pass_plain_target(pass) ||
         (pass->dst.fmt != PLH_FMT_RGBA16 && pass->dst.fmt != PLH_FMT_RGBA16F))
-        return false;
+        return -1;
     const int n = pass->num_ops;
     int i = 0;
     *m = plh_mixplan{};
     m->delin = -1;
     for (;;) {
         if (m->n == PLH_MIX_MAX)
-            return false;
+            return -1;
         const int f = m->n;
         m->fetch[f] = m->lin[f] = -1;
         if (f > 0) {
             if (!(i < n && pass->ops[i].kind == PLH_OP_PLANE_FETCH))
-                return false;
+                return -1;
             m->fetch[f] = i++;
         }
         if (i < n && pass->ops[i].kind == PLH_OP_LINEARIZE)
             m->lin[f] = i++;
         if (!(i < n && pass->ops[i].kind == PLH_OP_MIX_ADD))
-            return false;
+            return -1;
         m->add[f] = i++;
         m->n++;
         if (i < n && pass->ops[i].kind == PLH_OP_MIX_END) {
@@ -835,9 +848,19 @@ static bool pass_mix_applies(plh_pass *pass, plh_mixplan *m)
         }
     }
     if (m->n < 2)
-        return false;
+        return -1;
     if (i < n && pass->ops[i].kind == PLH_OP_DELINEARIZE)
         m->delin = i++;
+    return i;
+}
+
+// Is this the blending pass k_pass_mix is written for? Fills pass->epi.
+static bool pass_mix_applies(plh_pass *pass)
+{
+    plh_mixplan m;
+    const int i = pass_mix_plan(pass, &m), n = pass->num_ops;
+    if (i < 0)
+        return false;
     pass->chain = plh_map_chain{ 0, -1, -1, -1, -1, -1, -1, 0, -1, -1, -1, 0 };
     pass->epi = plh_fast_epi{};
     if (pass->dst.fmt == PLH_FMT_RGBA16F)
@@ -856,8 +879,8 @@ static bool pass_has_tricubic(const plh_pass *pass)
     return false;
 }
 
-// the shape k_pass_native is written for
-static bool pass_native_applies(const plh_pass *pass, bool features = false)
+// the shape k_pass_native is written for (and, with `features`, k_pass_features)
+static bool pass_native_shape(const plh_pass *pass, bool features = false)
 {
     const plh_sampler_args &s = pass->s;
     if (!plh_switch(PLH_SW_PASS_NATIVE))
@@ -876,67 +899,6 @@ static bool pass_native_applies(const plh_pass *pass, bool features = false)
            !plh_pass_has_op(pass, PLH_OP_PEAK_DETECT) && !pass_has_tricubic(pass);
 }
 
-template <bool LITE>
-static void launch_pass_native(hipStream_t stream, const plh_pass *pass)
-{
-    const dim3 block(PASS_BW, PASS_BH);
-    const int cells_w = (pass->width + 1) / 2, bh = PASS_BH * PASS_ITERS;
-    const dim3 grid((cells_w + PASS_BW - 1) / PASS_BW, (pass->height + bh - 1) / bh);
-    const bool fs = pass->s.src.fmt == PLH_FMT_RGBA16F, fd = pass->dst.fmt == PLH_FMT_RGBA16F;
-    if (fs && fd)       PLH_LAUNCH_LAST((k_pass_native<LITE, true, true>), grid, block, 0, stream, *pass);
-    else if (fs)        PLH_LAUNCH_LAST((k_pass_native<LITE, true, false>), grid, block, 0, stream, *pass);
-    else if (fd)        PLH_LAUNCH_LAST((k_pass_native<LITE, false, true>), grid, block, 0, stream, *pass);
-    else                PLH_LAUNCH_LAST((k_pass_native<LITE, false, false>), grid, block, 0, stream, *pass);
-}
-
-static bool nearest_fast_ok(plh_pass *pass)
-{
-    // (0 = the generic kernel, as for bilinear)
-    if (!plh_switch(PLH_SW_BILIN_ITERS) || pass->s.type != PLH_SAMPLE_NEAREST ||
-        pass->s.address_mode != PLH_ADDRESS_CLAMP || pass->num_pre_ops || pass->transpose ||
-        (pass->s.src.fmt != PLH_FMT_RGBA16 && pass->s.src.fmt != PLH_FMT_RGBA16F))
-        return false;
-    plh_match_fast_epilogue(pass, true);
-    return pass->epi.enabled;
-}
-
-// 0: not eligible, else the number of cells per lane
-static int bilinear_fast_iters(plh_pass *pass)
-{
-    const int iters_env = plh_switch(PLH_SW_BILIN_ITERS);
-    if (!iters_env || pass->s.type != PLH_SAMPLE_BILINEAR ||
-        pass->s.address_mode != PLH_ADDRESS_CLAMP || pass->num_pre_ops || pass->transpose ||
-        (pass->s.src.fmt != PLH_FMT_RGBA16 && pass->s.src.fmt != PLH_FMT_RGBA16F))
-        return 0;
-    plh_match_fast_epilogue(pass, true);
-    if (!pass->epi.enabled)
-        return 0;
-    return iters_env == 2 || iters_env == 4 ? iters_env : 1;
-}
-
-template <bool F16SRC>
-static void launch_bilinear_fast(hipStream_t stream, const plh_pass *pass, int iters)
-{
-    const int cells_w = (pass->width + pass->cell_padx + 1) / 2;
-    const int cells_h = (pass->height + pass->cell_pady + 1) / 2;
-    const dim3 block(BF_BW, BF_BH);
-    const int bh = BF_BH * iters;
-    const dim3 grid((cells_w + BF_BW - 1) / BF_BW, (cells_h + bh - 1) / bh);
-#define BF_LAUNCH(IT) do { \
-        if (pass->epi.has_alpha) \
-            PLH_LAUNCH_LAST((k_bilinear_fast<F16SRC, IT, true>), grid, block, 0, stream, *pass); \
-        else \
-            PLH_LAUNCH_LAST((k_bilinear_fast<F16SRC, IT, false>), grid, block, 0, stream, *pass); \
-    } while (0)
-    if (iters == 4)
-        BF_LAUNCH(4);
-    else if (iters == 2)
-        BF_LAUNCH(2);
-    else
-        BF_LAUNCH(1);
-#undef BF_LAUNCH
-}
-
 /* ------------------------------------------------------------------------ */
 
 int plh_launch_polar(hipStream_t stream, const plh_pass *pass);
@@ -948,13 +910,19 @@ extern "C" int plh_launch_deinterlace(plh_stream stream, const struct plh_pass *
 // k_pass_viz.hip: the variant with the colour map's diagnostics (and the Dolby Vision ops)
 int plh_launch_generic_viz(hipStream_t stream, const plh_pass *pass, bool cubic);
 
+// no sampler, or one texel / one hardware-bilinear footprint per pixel
+static bool pass_simple_sampler(const plh_pass *pass)
+{
+    return pass->s.type == PLH_SAMPLE_NONE || pass->s.type == PLH_SAMPLE_NEAREST ||
+           pass->s.type == PLH_SAMPLE_BILINEAR;
+}
+
 // the generic kernel (any sampler without a kernel of its own, any op list)
 static int plh_launch_generic(hipStream_t stream, const plh_pass *pass, bool cubic, bool dovi)
 {
     const dim3 block(PASS_BW, PASS_BH);
     const bool lite = plh_ops_lite(pass, 0, pass->num_ops);
-    const bool simple = pass->s.type == PLH_SAMPLE_NONE || pass->s.type == PLH_SAMPLE_NEAREST ||
-                        pass->s.type == PLH_SAMPLE_BILINEAR;
+    const bool simple = pass_simple_sampler(pass);
     // 2x2 cells share the bilinear footprint; everything else prefers the lighter 2x1 cells
     // (measured: 4K colour map 193 -> 168 us, plane copy 20.4 -> 18.8 us)
     int ch = pass->s.type == PLH_SAMPLE_BILINEAR && lite ? 2 : 1;
@@ -992,6 +960,83 @@ static int plh_launch_generic(hipStream_t stream, const plh_pass *pass, bool cub
     return plh_launch_status();
 }
 
+/* ---- the candidates for a 1:1 pass (launch_ladder.hiph), in the order of plh_launch_pass's table ---- */
+
+// A kernel with a <true> / <false> pair of instances: launch the one `which` picks as the pass's
+// last kernel (the kernel's arguments follow `stream`)
+#define PASS_LAUNCH_PAIR(kernel, which, grid, block, stream, ...)                                   \
+    do {                                                                                            \
+        if (which)                                                                                  \
+            PLH_LAUNCH_LAST(kernel<true>, grid, block, 0, stream, __VA_ARGS__);                     \
+        else                                                                                        \
+            PLH_LAUNCH_LAST(kernel<false>, grid, block, 0, stream, __VA_ARGS__);                    \
+    } while (0)
+
+// k_nearest_fast, k_bilinear_fast: PL_HIP_BILIN_ITERS cells per lane (0 = the generic kernel, for
+// either) of a clamped sampler of `type` on a packed 16-bit source, nothing in front of it; 0: not such a pass
+static int pass_fast_cells(const plh_pass *pass, int type)
+{
+    const int iters_env = plh_switch(PLH_SW_BILIN_ITERS);
+    if (!iters_env || pass->s.type != type ||
+        pass->s.address_mode != PLH_ADDRESS_CLAMP || pass->num_pre_ops || pass->transpose ||
+        (pass->s.src.fmt != PLH_FMT_RGBA16 && pass->s.src.fmt != PLH_FMT_RGBA16F))
+        return 0;
+    return iters_env == 2 || iters_env == 4 ? iters_env : 1;
+}
+
+static bool nearest_fast_applies(plh_pass *pass)
+{
+    if (!pass_fast_cells(pass, PLH_SAMPLE_NEAREST))
+        return false;
+    plh_match_fast_epilogue(pass, true);
+    return pass->epi.enabled;
+}
+
+static int launch_nearest_fast(hipStream_t stream, const plh_pass *pass)
+{
+    const int cells_w = (pass->width + pass->cell_padx + 1) / 2;
+    const dim3 grid((cells_w + BF_BW - 1) / BF_BW, (pass->height + BF_BH * NF_ROWS - 1) / (BF_BH * NF_ROWS));
+    PASS_LAUNCH_PAIR(k_nearest_fast, pass->s.src.fmt == PLH_FMT_RGBA16F, grid, dim3(BF_BW, BF_BH), stream, *pass);
+    return plh_launch_status();
+}
+
+static bool bilinear_fast_applies(plh_pass *pass)
+{
+    if (!pass_fast_cells(pass, PLH_SAMPLE_BILINEAR))
+        return false;
+    plh_match_fast_epilogue(pass, true);
+    return pass->epi.enabled;
+}
+
+// k_bilinear_fast's instance for the source's texels, the cells per lane and the alpha override
+template <bool F16SRC>
+static plh_pass_launch_fn *bilinear_fast_cells_instance(const plh_pass *pass)
+{
+#define BF(IT) return pass->epi.has_alpha ? plh_launch_last_lds<k_bilinear_fast<F16SRC, IT, true>> \
+                                          : plh_launch_last_lds<k_bilinear_fast<F16SRC, IT, false>>
+    switch (pass_fast_cells(pass, PLH_SAMPLE_BILINEAR)) {
+    case 4:  BF(4);
+    case 2:  BF(2);
+    default: BF(1);
+    }
+#undef BF
+}
+
+static plh_pass_launch_fn *bilinear_fast_instance(const plh_pass *pass)
+{
+    return pass->s.src.fmt == PLH_FMT_RGBA16F ? bilinear_fast_cells_instance<true>(pass)
+                                              : bilinear_fast_cells_instance<false>(pass);
+}
+
+static int launch_bilinear_fast(hipStream_t stream, const plh_pass *pass)
+{
+    const int cells_w = (pass->width + pass->cell_padx + 1) / 2;
+    const int cells_h = (pass->height + pass->cell_pady + 1) / 2;
+    const int bh = BF_BH * pass_fast_cells(pass, PLH_SAMPLE_BILINEAR);
+    const dim3 grid((cells_w + BF_BW - 1) / BF_BW, (cells_h + bh - 1) / bh);
+    return bilinear_fast_instance(pass)(grid, dim3(BF_BW, BF_BH), 0, stream, *pass);
+}
+
 // grid of the kernels that give a lane two horizontally adjacent pixels of a 1:1 pass, in
 // workgroups of PASS_BW x PASS_BH lanes (k_pass_merge, k_pass_mix, k_pass_features)
 static dim3 pass_pair_grid(const plh_pass *pass)
@@ -999,17 +1044,118 @@ static dim3 pass_pair_grid(const plh_pass *pass)
     return dim3(((pass->width + 1) / 2 + PASS_BW - 1) / PASS_BW, (pass->height + PASS_BH - 1) / PASS_BH);
 }
 
-// A specialised kernel with a <true> / <false> pair of instances, once its test has passed: name it
-// in the trace, launch the instance `which` picks as the pass's last kernel and return the status.
-#define PASS_RETURN_LAUNCH(kernel, which, grid, block, ...)                                         \
-    do {                                                                                            \
-        plh_trace_kernel(#kernel);                                                                  \
-        if (which)                                                                                  \
-            PLH_LAUNCH_LAST(kernel<true>, grid, block, 0, stream, __VA_ARGS__);                     \
-        else                                                                                        \
-            PLH_LAUNCH_LAST(kernel<false>, grid, block, 0, stream, __VA_ARGS__);                    \
-        return plh_launch_status();                                                                 \
+static int launch_pass_merge(hipStream_t stream, const plh_pass *pass)
+{
+    plh_merge m;
+    pass_merge_plan(pass, &m);
+    PASS_LAUNCH_PAIR(k_pass_merge, pass->dst.fmt == PLH_FMT_RGBA16F, pass_pair_grid(pass), dim3(PASS_BW, PASS_BH),
+                     stream, *pass, m);
+    return plh_launch_status();
+}
+
+static int launch_pass_mix(hipStream_t stream, const plh_pass *pass)
+{
+    plh_mixplan m;
+    pass_mix_plan(pass, &m);
+    PASS_LAUNCH_PAIR(k_pass_mix, pass->dst.fmt == PLH_FMT_RGBA16F, pass_pair_grid(pass), dim3(PASS_BW, PASS_BH),
+                     stream, *pass, m);
+    return plh_launch_status();
+}
+
+static bool pass_features_applies(plh_pass *pass) { return pass_native_shape(pass, true); }
+
+static int launch_pass_features(hipStream_t stream, const plh_pass *pass)
+{
+    PASS_LAUNCH_PAIR(k_pass_features, pass->s.src.fmt == PLH_FMT_RGBA16F, pass_pair_grid(pass), dim3(PASS_BW, PASS_BH),
+                     stream, *pass);
+    return plh_launch_status();
+}
+
+// k_pass_chain: k_pass_native's shape with an op list that is a map chain -- into rgba16 every chain,
+// into the rgba16hf intermediate the ones without contrast recovery
+static bool pass_chain_applies(plh_pass *pass)
+{
+    if (!pass_native_shape(pass))
+        return false;
+    plh_match_map_chain(pass, true, true, true);
+    plh_map_chain &c = pass->chain;
+    if (!c.enabled || (pass->dst.fmt != PLH_FMT_RGBA16 && c.contrast_recovery))
+        return false;
+    if (pass->dst.fmt == PLH_FMT_RGBA16) {
+        // the tone curve's table in LDS where it fits
+        c.tone_lds = 0;
+        if (c.tone >= 0 && pass->ops[c.tone].i0 >= 2 && pass->ops[c.tone].ptr) {
+            const int n = (int) pass->ops[c.tone].f[8] + 1;
+            if (n >= 2 && n <= PQSEG_TONE_MAX)
+                c.tone_lds = n;
+        }
+    }
+    return true;
+}
+
+static int launch_pass_chain(hipStream_t stream, const plh_pass *pass)
+{
+    const dim3 block(PASS_BW, PASS_BH);
+    const bool f16 = pass->s.src.fmt == PLH_FMT_RGBA16F;
+    if (pass->dst.fmt == PLH_FMT_RGBA16F) {
+        // (two pixels per lane: into the f16 intermediate the chain is short -- decode, linearize,
+        // [sigmoidize] -- and the pass moves 16 bytes per pixel: 16-byte loads and stores. 4K:
+        // 40.8 -> 35.5 us, 1080p unchanged, profiles/r05_33)
+        const int cells_w = (pass->width + 1) / 2;
+        const dim3 grid((cells_w + PASS_BW - 1) / PASS_BW, (pass->height + PASS_BH - 1) / PASS_BH);
+        if (f16) PLH_LAUNCH_LAST((k_pass_chain<true, 2, false, true>), grid, block, 0, stream, *pass);
+        else     PLH_LAUNCH_LAST((k_pass_chain<false, 2, false, true>), grid, block, 0, stream, *pass);
+        return plh_launch_status();
+    }
+    // (The PQ pair as piecewise cubics in LDS, pqseg.hiph, was tried here as k_pass_chain_seg and
+    // dropped: 14 % fewer vector instructions and the same time -- 94.5 us against 93.5 with the
+    // tables staged per 64 x 4 pixels, 100 / 102 with two / eight rows per workgroup, whose
+    // gathers then wait for the previous row's store, 119 with two pixels per lane
+    // (profiles/r06_16_seg_ab.txt, r06_17_seg_ab.txt). At eight waves per SIMD this pass is
+    // bound by the latency chain load -> tone gather -> gamut gathers -> store, not by
+    // instruction issue; k_polar_mx at four waves per SIMD is, and gains 14 %.)
+    const int cells_w = (pass->width + CHAIN_NP - 1) / CHAIN_NP;
+    const dim3 grid((cells_w + PASS_BW - 1) / PASS_BW, (pass->height + PASS_BH - 1) / PASS_BH);
+    const size_t shmem = (size_t) pass->chain.tone_lds * 4;
+    if (pass->chain.contrast_recovery) {
+        if (f16) PLH_LAUNCH_LAST((k_pass_chain<true, CHAIN_NP, true>), grid, block, shmem, stream, *pass);
+        else     PLH_LAUNCH_LAST((k_pass_chain<false, CHAIN_NP, true>), grid, block, shmem, stream, *pass);
+    } else {
+        if (f16) PLH_LAUNCH_LAST((k_pass_chain<true, CHAIN_NP, false>), grid, block, shmem, stream, *pass);
+        else     PLH_LAUNCH_LAST((k_pass_chain<false, CHAIN_NP, false>), grid, block, shmem, stream, *pass);
+    }
+    return plh_launch_status();
+}
+
+// k_pass_native: the same shape, any op list, interpreted
+static bool pass_native_applies(plh_pass *pass) { return pass_native_shape(pass); }
+
+static int launch_pass_native(hipStream_t stream, const plh_pass *pass)
+{
+    const dim3 block(PASS_BW, PASS_BH);
+    const int cells_w = (pass->width + 1) / 2, bh = PASS_BH * PASS_ITERS;
+    const dim3 grid((cells_w + PASS_BW - 1) / PASS_BW, (pass->height + bh - 1) / bh);
+    const bool fs = pass->s.src.fmt == PLH_FMT_RGBA16F, fd = pass->dst.fmt == PLH_FMT_RGBA16F;
+#define NATIVE(LITE) do { \
+        if (fs && fd)   PLH_LAUNCH_LAST((k_pass_native<LITE, true, true>), grid, block, 0, stream, *pass); \
+        else if (fs)    PLH_LAUNCH_LAST((k_pass_native<LITE, true, false>), grid, block, 0, stream, *pass); \
+        else if (fd)    PLH_LAUNCH_LAST((k_pass_native<LITE, false, true>), grid, block, 0, stream, *pass); \
+        else            PLH_LAUNCH_LAST((k_pass_native<LITE, false, false>), grid, block, 0, stream, *pass); \
     } while (0)
+    if (plh_ops_lite(pass, 0, pass->num_ops))
+        NATIVE(true);
+    else
+        NATIVE(false);
+#undef NATIVE
+    return plh_launch_status();
+}
+
+// k_pass_generic: every pass that has come this far
+static int launch_pass_generic(hipStream_t stream, const plh_pass *pass)
+{
+    return plh_launch_generic(stream, pass, pass_has_tricubic(pass), false);
+}
+#undef PASS_LAUNCH_PAIR
 
 extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
 {
@@ -1032,12 +1178,8 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
     // lut3d_tricubic lives in one variant of the generic kernel: such a colour map must be its
     // own pass (the renderer arranges that; a hand-built shader samples from an FBO first)
     const bool cubic = pass_has_tricubic(pass);
-    if (cubic) {
-        const bool simple = pass->s.type == PLH_SAMPLE_NONE || pass->s.type == PLH_SAMPLE_NEAREST ||
-                            pass->s.type == PLH_SAMPLE_BILINEAR;
-        if (!simple || measuring || mixing)
-            return -1004;
-    }
+    if (cubic && (!pass_simple_sampler(pass) || measuring || mixing))
+        return -1004;
 
     // Dolby Vision ops exist in one variant of the generic kernel only: such a pass (the
     // renderer's decoding pass of a Dolby Vision frame) goes straight there, past every
@@ -1081,111 +1223,19 @@ extern "C" int plh_launch_pass(plh_stream stream_, const struct plh_pass *pass)
     if (measuring)
         return plh_launch_peak(stream, pass);
 
-    // The specialised kernels, in the order they are tried. Each matches on a copy of the pass,
-    // which its `*_applies` test fills in (epi, chain) for its kernel alone.
-    {
-        plh_pass local = *pass;
-        if (nearest_fast_ok(&local)) {
-            const int cells_w = (local.width + local.cell_padx + 1) / 2;
-            const dim3 grid((cells_w + BF_BW - 1) / BF_BW,
-                            (local.height + BF_BH * NF_ROWS - 1) / (BF_BH * NF_ROWS));
-            PASS_RETURN_LAUNCH(k_nearest_fast, local.s.src.fmt == PLH_FMT_RGBA16F,
-                               grid, dim3(BF_BW, BF_BH), local);
-        }
-    }
-
-    {
-        plh_pass local = *pass;
-        const int iters = bilinear_fast_iters(&local);
-        if (iters) {
-            plh_trace_kernel("k_bilinear_fast");
-            if (local.s.src.fmt == PLH_FMT_RGBA16F)
-                launch_bilinear_fast<true>(stream, &local, iters);
-            else
-                launch_bilinear_fast<false>(stream, &local, iters);
-            return plh_launch_status();
-        }
-    }
-
-    {
-        plh_pass local = *pass;
-        plh_merge m;
-        if (pass_merge_applies(&local, &m))
-            PASS_RETURN_LAUNCH(k_pass_merge, local.dst.fmt == PLH_FMT_RGBA16F,
-                               pass_pair_grid(&local), dim3(PASS_BW, PASS_BH), local, m);
-    }
-
-    {
-        plh_pass local = *pass;
-        plh_mixplan mp;
-        if (pass_mix_applies(&local, &mp))
-            PASS_RETURN_LAUNCH(k_pass_mix, local.dst.fmt == PLH_FMT_RGBA16F,
-                               pass_pair_grid(&local), dim3(PASS_BW, PASS_BH), local, mp);
-    }
-
-    if (pass_native_applies(pass, true))
-        PASS_RETURN_LAUNCH(k_pass_features, pass->s.src.fmt == PLH_FMT_RGBA16F,
-                           pass_pair_grid(pass), dim3(PASS_BW, PASS_BH), *pass);
-
-    if (pass_native_applies(pass)) {
-        plh_pass local = *pass;
-        plh_match_map_chain(&local, true, true, true);
-        plh_trace_kernel(local.chain.enabled && (local.dst.fmt == PLH_FMT_RGBA16 || !local.chain.contrast_recovery)
-                         ? "k_pass_chain" : "k_pass_native");
-        if (local.chain.enabled && local.dst.fmt == PLH_FMT_RGBA16F && !local.chain.contrast_recovery) {
-            // (two pixels per lane: into the f16 intermediate the chain is short -- decode, linearize,
-            // [sigmoidize] -- and the pass moves 16 bytes per pixel: 16-byte loads and stores. 4K:
-            // 40.8 -> 35.5 us, 1080p unchanged, profiles/r05_33)
-            const dim3 block(PASS_BW, PASS_BH);
-            const int cells_w = (local.width + 1) / 2;
-            const dim3 grid((cells_w + PASS_BW - 1) / PASS_BW, (local.height + PASS_BH - 1) / PASS_BH);
-            if (local.s.src.fmt == PLH_FMT_RGBA16F)
-                PLH_LAUNCH_LAST((k_pass_chain<true, 2, false, true>), grid, block, 0, stream, local);
-            else
-                PLH_LAUNCH_LAST((k_pass_chain<false, 2, false, true>), grid, block, 0, stream, local);
-        } else if (local.chain.enabled && local.dst.fmt == PLH_FMT_RGBA16) {
-            const dim3 block(PASS_BW, PASS_BH);
-            const int cells_w = (local.width + CHAIN_NP - 1) / CHAIN_NP;
-            const dim3 grid((cells_w + PASS_BW - 1) / PASS_BW, (local.height + PASS_BH - 1) / PASS_BH);
-            const bool f16 = local.s.src.fmt == PLH_FMT_RGBA16F;
-            // (The PQ pair as piecewise cubics in LDS, pqseg.hiph, was tried here as k_pass_chain_seg and
-            // dropped: 14 % fewer vector instructions and the same time -- 94.5 us against 93.5 with the
-            // tables staged per 64 x 4 pixels, 100 / 102 with two / eight rows per workgroup, whose
-            // gathers then wait for the previous row's store, 119 with two pixels per lane
-            // (profiles/r06_16_seg_ab.txt, r06_17_seg_ab.txt). At eight waves per SIMD this pass is
-            // bound by the latency chain load -> tone gather -> gamut gathers -> store, not by
-            // instruction issue; k_polar_mx at four waves per SIMD is, and gains 14 %.)
-            // the tone curve's table in LDS where it fits
-            size_t shmem = 0;
-            local.chain.tone_lds = 0;
-            {
-                const int it = local.chain.tone;
-                if (it >= 0 && local.ops[it].i0 >= 2 && local.ops[it].ptr) {
-                    const int n = (int) local.ops[it].f[8] + 1;
-                    if (n >= 2 && n <= PQSEG_TONE_MAX) {
-                        local.chain.tone_lds = n;
-                        shmem = (size_t) n * 4;
-                    }
-                }
-            }
-            if (local.chain.contrast_recovery) {
-                if (f16) PLH_LAUNCH_LAST((k_pass_chain<true, CHAIN_NP, true>), grid, block, shmem, stream, local);
-                else     PLH_LAUNCH_LAST((k_pass_chain<false, CHAIN_NP, true>), grid, block, shmem, stream, local);
-            } else {
-                if (f16) PLH_LAUNCH_LAST((k_pass_chain<true, CHAIN_NP, false>), grid, block, shmem, stream, local);
-                else     PLH_LAUNCH_LAST((k_pass_chain<false, CHAIN_NP, false>), grid, block, shmem, stream, local);
-            }
-        } else if (plh_ops_lite(pass, 0, pass->num_ops))
-            launch_pass_native<true>(stream, pass);
-        else
-            launch_pass_native<false>(stream, pass);
-        return plh_launch_status();
-    }
-
-    plh_trace_kernel("k_pass_generic");
-    return plh_launch_generic(stream, pass, cubic, false);
+    // The kernels for every other pass, in the order they are tried
+    static const plh_candidate candidates[] = {
+        { "k_nearest_fast",  nearest_fast_applies,  launch_nearest_fast },   // nearest / bilinear fetch + the fused epilogue
+        { "k_bilinear_fast", bilinear_fast_applies, launch_bilinear_fast },
+        { "k_pass_merge",    pass_merge_applies,    launch_pass_merge },     // texel for texel: a planar frame assembled
+        { "k_pass_mix",      pass_mix_applies,      launch_pass_mix },       // ... cached frames blended
+        { "k_pass_features", pass_features_applies, launch_pass_features },  // ... the feature plane
+        { "k_pass_chain",    pass_chain_applies,    launch_pass_chain },     // ... a map chain as straight-line code
+        { "k_pass_native",   pass_native_applies,   launch_pass_native },    // ... any op list, interpreted
+        { "k_pass_generic",  plh_applies_always,    launch_pass_generic },   // every pass
+    };
+    return plh_launch_first(candidates, stream, pass);
 }
-#undef PASS_RETURN_LAUNCH
 
 // Test hook (tests/test_chain_match.py, CPU): plh_match_map_chain on an op list described by its
 // kinds and one flag word per op -- TONE_MAP: 1 = contrast recovery; GAMUT_LUT: 1 = tricubic;
@@ -1253,7 +1303,8 @@ int plh_test_match_mix(const int *kinds, int n, int dst_fmt, int sampler, int *o
         }
     }
     plh_mixplan m;
-    const bool ok = pass_mix_applies(&pass, &m);
+    pass_mix_plan(&pass, &m);
+    const bool ok = pass_mix_applies(&pass);
     out[0] = ok ? m.n : 0;
     out[1] = m.delin;
     out[2] = pass.epi.enabled;

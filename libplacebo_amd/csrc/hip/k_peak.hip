@@ -16,6 +16,7 @@
  */
 #include "colorops.hiph"
 #include "samplers.hiph"
+#include "launch_ladder.hiph"
 
 #define PEAK_BW 16
 #define PEAK_BH 16
@@ -821,8 +822,8 @@ void k_peak_tiles(const plh_pass p_)
         __hip_atomic_store(&mailbox[PLH_PEAK_WORDS], p.peak_ticket, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// the shape k_peak_fast is written for
-static bool peak_fast_applies(const plh_pass *pass)
+// the shape k_peak_fast is written for (a candidate's test, launch_ladder.hiph; it fills nothing in)
+static bool peak_fast_applies(plh_pass *pass)
 {
     const plh_sampler_args &s = pass->s;
     if (!plh_switch(PLH_SW_PEAK_FAST))
@@ -906,71 +907,114 @@ void k_peak_fold(uint32_t *dst, uint32_t *scratch, uint32_t *mailbox, uint32_t t
     }
 }
 
-int plh_launch_peak(hipStream_t stream, const plh_pass *pass)
+/* ---- the candidates for a measuring pass (launch_ladder.hiph), in the order of plh_launch_peak's table ---- */
+
+// the pass's 16 x 16 tiles, and the launch shape of the kernels that give a wave one of them
+static int peak_tile_count(const plh_pass *pass)
 {
-    const int tiles = ((pass->width + PEAK_BW - 1) / PEAK_BW) * ((pass->height + PEAK_BH - 1) / PEAK_BH);
-    const dim3 block(64 * PEAK_WAVES);
-    const dim3 grid((tiles + PEAK_WAVES - 1) / PEAK_WAVES);
-    if (!pass->peak_buf || !pass->peak_scratch)
-        return -1002;
-    int pk_op = pass->num_ops;
+    return ((pass->width + PEAK_BW - 1) / PEAK_BW) * ((pass->height + PEAK_BH - 1) / PEAK_BH);
+}
+
+static dim3 peak_grid(const plh_pass *pass) { return dim3((peak_tile_count(pass) + PEAK_WAVES - 1) / PEAK_WAVES); }
+static dim3 peak_block() { return dim3(64 * PEAK_WAVES); }
+
+// index of the PEAK_DETECT op (num_ops: there is none)
+static int peak_op(const plh_pass *pass)
+{
     for (int i = 0; i < pass->num_ops; i++) {
-        if (pass->ops[i].kind == PLH_OP_PEAK_DETECT) {
-            pk_op = i;
-            break;
-        }
+        if (pass->ops[i].kind == PLH_OP_PEAK_DETECT)
+            return i;
     }
-    const int trc = pk_op < pass->num_ops ? pass->ops[pk_op].i0 : -1;
-    const bool feat_target = pass->dst.ptr && pass->dst.fmt == PLH_FMT_R16F;
-    // (the feature plane: PEAK_DETECT FEATURES of a linear image, or PEAK_DETECT LINEARIZE FEATURES of PQ)
-    const bool feat_ok = !feat_target || pass->num_ops == 2 || pass->ops[1].i0 == TRC_PQ;
-    // what k_peak_tiles is instantiated for: a PQ source's flags (the clamp, no rescale), a
-    // PLANE_MAP of 3 or 4 components (what the renderer's planes have; anything else has k_peak_fast)
-    const bool pq_plain = trc != TRC_PQ || pass->ops[pk_op].i1 == PLH_TRC_CLAMP0;
-    const bool map_ok = pass->ops[0].kind != PLH_OP_PLANE_MAP || pass->ops[0].i1 >= 3;
-    if (peak_fast_applies(pass) && plh_switch(PLH_SW_PEAK_TILES) && feat_ok && pass->width >= 2 &&
-        (trc == TRC_PQ || trc == TRC_LINEAR) && pq_plain && map_ok) {
-        plh_trace_kernel("k_peak_tiles");
-        // k_peak_tiles folds its own result (no k_peak_fold behind it)
-        const bool f16 = pass->s.src.fmt == PLH_FMT_RGBA16F, store = pass->dst.ptr != NULL, pq = trc == TRC_PQ;
-        const int per_slice = (tiles + PEAK_SLICES - 1) / PEAK_SLICES;
-        // (two tiles per wave, at most 8 workgroups per CU. Measured beside the metric's scaler and
-        // alone, 1080p and 4K, profiles/r05_06_peak_groups.txt: fewer, longer-lived workgroups suit
-        // the former, more the latter; a cap of 170 per slice is the setting that loses neither)
-        int groups = (per_slice + 2 * PEAK_WAVES - 1) / (2 * PEAK_WAVES);
-        groups = groups < 1 ? 1 : groups > 170 ? 170 : groups;
-        const dim3 tgrid(PEAK_SLICES * groups);
-#define PEAK_TILES_GO(F, S, Q) PLH_LAUNCH_LAST((k_peak_tiles<F, S, Q>), tgrid, block, 0, stream, *pass)
-        if (f16 && feat_target) { if (pq) PEAK_TILES_GO(true, 2, true); else PEAK_TILES_GO(true, 2, false); }
-        else if (feat_target)   { if (pq) PEAK_TILES_GO(false, 2, true); else PEAK_TILES_GO(false, 2, false); }
-        else if (f16 && store)  { if (pq) PEAK_TILES_GO(true, 1, true); else PEAK_TILES_GO(true, 1, false); }
-        else if (f16)           { if (pq) PEAK_TILES_GO(true, 0, true); else PEAK_TILES_GO(true, 0, false); }
-        else if (store)         { if (pq) PEAK_TILES_GO(false, 1, true); else PEAK_TILES_GO(false, 1, false); }
-        else                    { if (pq) PEAK_TILES_GO(false, 0, true); else PEAK_TILES_GO(false, 0, false); }
+    return pass->num_ops;
+}
+
+// the r16hf feature plane as the target: PEAK_DETECT [LINEARIZE] FEATURES
+static bool peak_feature_target(const plh_pass *pass) { return pass->dst.ptr && pass->dst.fmt == PLH_FMT_R16F; }
+
+// k_peak_tiles: k_peak_fast's shape where an instance exists for it
+static bool peak_tiles_applies(plh_pass *pass)
+{
+    // (k_peak_fast's shape has a PEAK_DETECT op, as ops[0] or behind a PLANE_MAP)
+    if (!peak_fast_applies(pass) || !plh_switch(PLH_SW_PEAK_TILES) || pass->width < 2)
+        return false;
+    const plh_op &pk = pass->ops[peak_op(pass)];
+    // a PQ source's flags (the clamp, no rescale; other flags have k_peak_fast) or a linear one
+    if (pk.i0 == TRC_PQ ? pk.i1 != PLH_TRC_CLAMP0 : pk.i0 != TRC_LINEAR)
+        return false;
+    // the feature plane: PEAK_DETECT FEATURES of a linear image, or PEAK_DETECT LINEARIZE FEATURES of PQ
+    if (peak_feature_target(pass) && pass->num_ops != 2 && !(pass->num_ops > 1 && pass->ops[1].i0 == TRC_PQ))
+        return false;
+    // a PLANE_MAP of 3 or 4 components (what the renderer's planes have; anything else has k_peak_fast)
+    return pass->ops[0].kind != PLH_OP_PLANE_MAP || pass->ops[0].i1 >= 3;
+}
+
+// k_peak_tiles folds its own result (no k_peak_fold behind it): the pass's last kernel
+static int launch_peak_tiles(hipStream_t stream, const plh_pass *pass)
+{
+    const bool f16 = pass->s.src.fmt == PLH_FMT_RGBA16F, store = pass->dst.ptr != NULL;
+    const bool feat_target = peak_feature_target(pass), pq = pass->ops[peak_op(pass)].i0 == TRC_PQ;
+    const int per_slice = (peak_tile_count(pass) + PEAK_SLICES - 1) / PEAK_SLICES;
+    // (two tiles per wave, at most 8 workgroups per CU. Measured beside the metric's scaler and
+    // alone, 1080p and 4K, profiles/r05_06_peak_groups.txt: fewer, longer-lived workgroups suit
+    // the former, more the latter; a cap of 170 per slice is the setting that loses neither)
+    int groups = (per_slice + 2 * PEAK_WAVES - 1) / (2 * PEAK_WAVES);
+    groups = groups < 1 ? 1 : groups > 170 ? 170 : groups;
+    const dim3 tgrid(PEAK_SLICES * groups);
+#define PEAK_TILES_GO(F, S, Q) PLH_LAUNCH_LAST((k_peak_tiles<F, S, Q>), tgrid, peak_block(), 0, stream, *pass)
+    if (f16 && feat_target) { if (pq) PEAK_TILES_GO(true, 2, true); else PEAK_TILES_GO(true, 2, false); }
+    else if (feat_target)   { if (pq) PEAK_TILES_GO(false, 2, true); else PEAK_TILES_GO(false, 2, false); }
+    else if (f16 && store)  { if (pq) PEAK_TILES_GO(true, 1, true); else PEAK_TILES_GO(true, 1, false); }
+    else if (f16)           { if (pq) PEAK_TILES_GO(true, 0, true); else PEAK_TILES_GO(true, 0, false); }
+    else if (store)         { if (pq) PEAK_TILES_GO(false, 1, true); else PEAK_TILES_GO(false, 1, false); }
+    else                    { if (pq) PEAK_TILES_GO(false, 0, true); else PEAK_TILES_GO(false, 0, false); }
 #undef PEAK_TILES_GO
-        return plh_launch_status();
-    }
-    if (peak_fast_applies(pass)) {
-        plh_trace_kernel("k_peak_fast");
-        const bool f16 = pass->s.src.fmt == PLH_FMT_RGBA16F, store = pass->dst.ptr != NULL;
-        const bool feat = store && pass->dst.fmt == PLH_FMT_R16F;
-        if (f16 && feat)        hipLaunchKernelGGL((k_peak_fast<true, 2>), grid, block, 0, stream, *pass);
-        else if (feat)          hipLaunchKernelGGL((k_peak_fast<false, 2>), grid, block, 0, stream, *pass);
-        else if (f16 && store)  hipLaunchKernelGGL((k_peak_fast<true, 1>), grid, block, 0, stream, *pass);
-        else if (f16)           hipLaunchKernelGGL((k_peak_fast<true, 0>), grid, block, 0, stream, *pass);
-        else if (store)         hipLaunchKernelGGL((k_peak_fast<false, 1>), grid, block, 0, stream, *pass);
-        else                    hipLaunchKernelGGL((k_peak_fast<false, 0>), grid, block, 0, stream, *pass);
-    } else if (plh_ops_lite(pass, 0, pk_op) && plh_ops_lite(pass, PL_MIN_INT(pk_op + 1, pass->num_ops), pass->num_ops)) {
-        plh_trace_kernel("k_pass_peak");
-        hipLaunchKernelGGL(k_pass_peak<true>, grid, block, 0, stream, *pass);
-    } else {
-        plh_trace_kernel("k_pass_peak");
-        hipLaunchKernelGGL(k_pass_peak<false>, grid, block, 0, stream, *pass);
-    }
+    return plh_launch_status();
+}
+
+// behind k_peak_fast and k_pass_peak: the fold of their partial buffers, the pass's last kernel
+static int launch_peak_fold(hipStream_t stream, const plh_pass *pass)
+{
     static_assert(PLH_PEAK_COPIES % FOLD_GROUPS == 0, "copy groups");
     PLH_LAUNCH_LAST(k_peak_fold, dim3((PLH_PEAK_WORDS + FOLD_WORDS - 1) / FOLD_WORDS),
                        dim3(FOLD_WORDS * FOLD_GROUPS), 0, stream, (uint32_t *) pass->peak_buf,
                        (uint32_t *) pass->peak_scratch, (uint32_t *) pass->peak_mailbox,
                        pass->peak_ticket);
     return plh_launch_status();
+}
+
+static int launch_peak_fast(hipStream_t stream, const plh_pass *pass)
+{
+    const dim3 grid = peak_grid(pass), block = peak_block();
+    const bool f16 = pass->s.src.fmt == PLH_FMT_RGBA16F, store = pass->dst.ptr != NULL;
+    const bool feat = peak_feature_target(pass);
+    if (f16 && feat)        hipLaunchKernelGGL((k_peak_fast<true, 2>), grid, block, 0, stream, *pass);
+    else if (feat)          hipLaunchKernelGGL((k_peak_fast<false, 2>), grid, block, 0, stream, *pass);
+    else if (f16 && store)  hipLaunchKernelGGL((k_peak_fast<true, 1>), grid, block, 0, stream, *pass);
+    else if (f16)           hipLaunchKernelGGL((k_peak_fast<true, 0>), grid, block, 0, stream, *pass);
+    else if (store)         hipLaunchKernelGGL((k_peak_fast<false, 1>), grid, block, 0, stream, *pass);
+    else                    hipLaunchKernelGGL((k_peak_fast<false, 0>), grid, block, 0, stream, *pass);
+    return launch_peak_fold(stream, pass);
+}
+
+// k_pass_peak: the interpreter around the measurement -- every measuring pass
+static int launch_pass_peak(hipStream_t stream, const plh_pass *pass)
+{
+    const int pk_op = peak_op(pass);
+    if (plh_ops_lite(pass, 0, pk_op) && plh_ops_lite(pass, PL_MIN_INT(pk_op + 1, pass->num_ops), pass->num_ops))
+        hipLaunchKernelGGL(k_pass_peak<true>, peak_grid(pass), peak_block(), 0, stream, *pass);
+    else
+        hipLaunchKernelGGL(k_pass_peak<false>, peak_grid(pass), peak_block(), 0, stream, *pass);
+    return launch_peak_fold(stream, pass);
+}
+
+int plh_launch_peak(hipStream_t stream, const plh_pass *pass)
+{
+    if (!pass->peak_buf || !pass->peak_scratch)
+        return -1002;
+    static const plh_candidate candidates[] = {
+        { "k_peak_tiles", peak_tiles_applies,  launch_peak_tiles },     // the measurement kept on chip, folded by the last workgroup
+        { "k_peak_fast",  peak_fast_applies,   launch_peak_fast },      // a wave per tile, partial buffers
+        { "k_pass_peak",  plh_applies_always,  launch_pass_peak },      // every measuring pass
+    };
+    return plh_launch_first(candidates, stream, pass);
 }

@@ -314,7 +314,6 @@ static int plh_launch_polar_pp(hipStream_t stream, const plh_pass *pass)
 }
 
 // k_polar: per-pixel weights, the recorded ops interpreted -- any polar pass
-static bool plh_polar_px_applies(plh_pass *) { return true; }
 
 // k_polar's instance for the tile's texels T, the component mask and anti-ringing
 template <typename T>
@@ -349,20 +348,13 @@ static int plh_launch_polar_px(hipStream_t stream, const plh_pass *pass)
 // The kernels for a polar pass, in the order they are tried; each on a copy of the pass of its own
 int plh_launch_polar(hipStream_t stream, const plh_pass *pass)
 {
-    static const struct { const char *name; plh_polar_applies_fn *applies; plh_polar_launch_fn *launch; } candidates[] = {
+    static const plh_candidate candidates[] = {
         { "k_polar_mxd", plh_polar_mxd_applies, plh_launch_polar_mxd },   // matrix pipe: the 2 : 1 downscale
         { "k_polar_mxr", plh_polar_mxr_applies, plh_launch_polar_mxr },   // ... the 3x, 4x, 3 : 2 upscales
         { "k_polar_mxp", plh_polar_mxp_applies, plh_launch_polar_mxp },   // ... the 2x upscale, persistent, commonest op shapes
         { "k_polar_mx",  plh_polar_mx_applies,  plh_launch_polar_mx },    // ... the 2x upscale, every op shape
         { "k_polar_pp",  plh_polar_pp_applies,  plh_launch_polar_pp },    // phase classes: every geometry with tables
-        { "k_polar",     plh_polar_px_applies,  plh_launch_polar_px },    // every pass
+        { "k_polar",     plh_applies_always,    plh_launch_polar_px },    // every pass
     };
-    for (const auto &c : candidates) {
-        plh_pass local = *pass;
-        if (c.applies(&local)) {
-            plh_trace_kernel(c.name);
-            return c.launch(stream, &local);
-        }
-    }
-    return -(int) hipErrorInvalidValue;     // (not reached: the last candidate takes every pass)
+    return plh_launch_first(candidates, stream, pass);
 }
