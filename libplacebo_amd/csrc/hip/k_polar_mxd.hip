@@ -172,9 +172,9 @@ void k_polar_mxd(const plh_pass p_)
                     *(uint32_t *) (d + MXD_PLANE) = (uint32_t) plh_f2h(t[2]) | ((uint32_t) plh_f2h(t[3]) << 16);
                     *(uint32_t *) (d + 2 * MXD_PLANE) = (uint32_t) plh_f2h(t[4]) | ((uint32_t) plh_f2h(t[5]) << 16);
                 } else {
-                    // rgba16hf: the f16 codes as they are; UNORM && PRE: the raw codes, converted in
-                    // place below
-                    const uint4 o = mx_pair_split_raw(w);
+                    // rgba16hf: the f16 codes as they are, held to the finite range (mx_tile.hiph);
+                    // UNORM && PRE: the raw codes, converted in place below
+                    const uint4 o = UNORM ? mx_pair_split_raw(w) : mx_pair_split_f16(w);
                     mx_pair_store<3>(tile, MXD_PLANE, ty[u] * MXD_PITCH, tp[u], o.x, o.y, o.z, 0);
                 }
             }

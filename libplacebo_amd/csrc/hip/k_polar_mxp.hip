@@ -184,7 +184,7 @@ void k_polar_mxp(const plh_pass p_)
             for (int u = 0; u < NV; u++) {
                 const uint4 w = v[u];
                 if (tid + u * NT < G::npairs)
-                    pair_store(ty(u), tp(u), mx_pair_split_raw(w));
+                    pair_store(ty(u), tp(u), mx_pair_split_f16(w));
             }
         } else if (simple) {
             // the plane as it is, or behind an identity PLANE_MAP: no interpreter walk
@@ -217,7 +217,7 @@ void k_polar_mxp(const plh_pass p_)
 #pragma unroll
             for (int u = 0; u < NV; u++) {
                 if (tid + u * NT < G::npairs)
-                    pair_store(ty(u), tp(u), mx_pair_pack(c[2 * u], c[2 * u + 1]));
+                    pair_store(ty(u), tp(u), mx_pair_pack(c[2 * u], c[2 * u + 1], unorm));
             }
         }
         return nx_dfx;

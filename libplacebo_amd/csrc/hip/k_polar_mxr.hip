@@ -135,7 +135,8 @@ void k_polar_mxr(const plh_pass p_)
 #pragma unroll
         for (int u = 0; u < MXR_NV; u++) {
             // (every tile: no edge test in front of the fix. The decode is this kernel's own -- plh_un16's
-            // quotient, f16 codes bit for bit behind a PLANE_MAP: not mx_pair_simple's instructions)
+            // quotient, f16 codes bit for bit -- held to the finite range, mx_finite2 -- behind a PLANE_MAP: not
+            // mx_pair_simple's instructions)
             const uint4 w = mx_pair_fix(v[u], sx[u], sw);
             const uint32_t q[4] = { w.x, w.y, w.z, w.w };
             uint32_t o[3];
@@ -151,7 +152,7 @@ void k_polar_mxr(const plh_pass p_)
                     }
                     o[k] = mx_pack(fa, fb);
                 } else {
-                    o[k] = k >= present ? mx_pack(om.f[k], om.f[k]) : (a | (b << 16));
+                    o[k] = k >= present ? mx_pack(om.f[k], om.f[k]) : mx_finite2(a | (b << 16));
                 }
             }
             if (tid + u * MXR_NT < MXR_NPAIRS) {
