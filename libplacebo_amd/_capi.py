@@ -890,6 +890,10 @@ def declare(lib):
         # (n_axis, n_across, row_size, pos[4][2], dir): may k_ortho_fast's one reflection serve a
         # mirrored pass (shader_sampling.c)
         fn("plh_test_ortho_one_reflection", C.c_int, C.c_int, C.c_int, C.c_int, P(C.c_float), C.c_int)
+    if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "plh_test_polar_band_plan"):
+        # (ratio_x, ratio_y, bound, texel bytes, LDS limit, out[5] = output tile w, h, ring rows, ring
+        # width, LDS bytes): k_polar_band's launch geometry, 0 = none (shader_sampling.c)
+        fn("plh_test_polar_band_plan", C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, P(C.c_int))
     if LIB_PATH == _DEFAULT_LIB_PATH or hasattr(lib, "pl_hip_create_swapchain"):
         # swapchain.h, hip_swapchain.h and renderer.h's pl_frame_from_swapchain
         sw = P(Swapchain)

@@ -337,8 +337,9 @@ static int plh_launch_polar_px(hipStream_t stream, const plh_pass *pass)
     const dim3 grid((pass->width + POLAR_BW - 1) / POLAR_BW, (pass->height + th - 1) / th);
     const size_t px = s.tile_fp32 ? sizeof(float4) : sizeof(uint2);
     const size_t shmem = 256 * sizeof(float2) + (size_t) s.tile_w * s.tile_h * px;
-    // (not reached: pl_shader_sample_polar, shader_sampling.c, fails a shader whose tile -- this sum --
-    // is above 160 KiB. It does size tiles of steep downscales above 64 KiB: plh_launch_last_lds asks)
+    // (not reached: pl_shader_sample_polar, shader_sampling.c, plans the band walk for a pass whose
+    // tile -- this sum -- is above 160 KiB. It does size tiles of steep downscales above 64 KiB:
+    // plh_launch_last_lds asks)
     if (shmem > 160 * 1024)
         return -1000;
     plh_pass_launch_fn *launch = s.tile_fp32 ? px_instance<float>(pass) : px_instance<__half>(pass);
@@ -354,7 +355,8 @@ int plh_launch_polar(hipStream_t stream, const plh_pass *pass)
         { "k_polar_mxp", plh_polar_mxp_applies, plh_launch_polar_mxp },   // ... the 2x upscale, persistent, commonest op shapes
         { "k_polar_mx",  plh_polar_mx_applies,  plh_launch_polar_mx },    // ... the 2x upscale, every op shape
         { "k_polar_pp",  plh_polar_pp_applies,  plh_launch_polar_pp },    // phase classes: every geometry with tables
-        { "k_polar",     plh_applies_always,    plh_launch_polar_px },    // every pass
+        { "k_polar_band", plh_polar_band_applies, plh_launch_polar_band }, // a pass with a band plan: no whole tile fits
+        { "k_polar",     plh_applies_always,    plh_launch_polar_px },    // every other pass
     };
     return plh_launch_first(candidates, stream, pass);
 }

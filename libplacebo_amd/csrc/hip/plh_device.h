@@ -180,6 +180,11 @@ struct plh_sampler_args {
     int32_t pp_n, pp_cells_w, pp_cells_h;   // host copies of pp->n, cells_w, cells_h
     int32_t pp_debug;       // profiling aid (PL_HIP_PP_DEBUG): 1 = no taps, 2 = no verify, 4 = no store
     struct plh_polar_mx mx; // matrix-pipe variant (enabled = 0: k_polar_pp)
+    // POLAR band plan (k_polar_band.hip; host: polar_band_plan, shader_sampling.c). band_rows != 0:
+    // the footprint is walked through an LDS ring of band_rows rows x band_w texels instead of
+    // being staged whole; a workgroup is band_out_w x band_out_h lanes, one output pixel each
+    int32_t band_rows, band_w;
+    int32_t band_out_w, band_out_h;
 
     // ORTHO: weights[256][row_stride] rows; N taps along `dir`
     const float *weights;   // device

@@ -20,7 +20,8 @@ extern "C" {
     X(NT_STORE,        "PL_HIP_NT_STORE",         1, "0: plain stores to unorm targets instead of streaming (non-temporal) ones") \
     X(POLAR_MFMA,      "PL_HIP_POLAR_MFMA",       1, "0: every polar pass on the bit-exact sequential-fma kernels instead of the matrix-pipe ones") \
     X(POLAR_PER_PIXEL, "PL_HIP_POLAR_PER_PIXEL",  0, "1: polar weights evaluated per pixel (k_polar) instead of from phase-class tables (k_polar_pp)") \
-    X(MX_PERSIST,      "PL_HIP_MX_PERSIST",       1, "0: k_polar_mx (a workgroup per tile) instead of k_polar_mxp (persistent workgroups)") \
+    X(POLAR_BAND,      "PL_HIP_POLAR_BAND",       0, "1: every polar pass on k_polar_band (the footprint walked through a ring of source rows) instead of only those whose footprint no other kernel can stage") \
+    X(MX_PERSIST,     "PL_HIP_MX_PERSIST",       1, "0: k_polar_mx (a workgroup per tile) instead of k_polar_mxp (persistent workgroups)") \
     X(MAP_CHAIN,       "PL_HIP_MAP_CHAIN",        1, "0: colour-management ops walked by the interpreter instead of the straight-line chain") \
     X(PQ_SEGMENTS,     "PL_HIP_PQ_SEGMENTS",      1, "0: the chain's PQ pair in closed form instead of piecewise cubics in LDS") \
     X(PQ_SEG_COPIES,   "PL_HIP_PQ_SEG_COPIES",    1, "1 | 2 | 4 | 8 | 16 copies of every piece of those cubics in k_polar_mx's LDS") \

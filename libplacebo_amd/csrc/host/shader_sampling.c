@@ -34,6 +34,24 @@ struct src_info {
     bool linear; // bound with LINEAR filtering
 };
 
+// Size of the source rect and of the output, as setup_src measures them (sampling.c:137-146)
+struct src_geometry {
+    float src_w, src_h;
+    int out_w, out_h;
+};
+
+static struct src_geometry src_geometry(const struct pl_sample_src *src)
+{
+    struct src_geometry g;
+    g.src_w = pl_rect_w(src->rect);
+    g.src_h = pl_rect_h(src->rect);
+    g.src_w = PL_DEF(g.src_w, (float) src->tex->params.w);
+    g.src_h = PL_DEF(g.src_h, (float) src->tex->params.h);
+    g.out_w = PL_DEF(src->new_w, (int) roundf(fabsf(g.src_w)));
+    g.out_h = PL_DEF(src->new_h, (int) roundf(fabsf(g.src_h)));
+    return g;
+}
+
 // Common source setup; mirrors setup_src (sampling.c:45-181)
 static bool setup_src(pl_shader sh, const struct pl_sample_src *src, struct src_info *out,
                       bool resizeable, enum filter_req req)
@@ -53,12 +71,9 @@ static bool setup_src(pl_shader sh, const struct pl_sample_src *src, struct src_
     }
     out->linear = req == REQ_LINEAR || (req == REQ_BEST && can_linear);
 
-    float src_w = pl_rect_w(src->rect), src_h = pl_rect_h(src->rect);
-    src_w = PL_DEF(src_w, (float) src->tex->params.w);
-    src_h = PL_DEF(src_h, (float) src->tex->params.h);
-
-    const int out_w = PL_DEF(src->new_w, (int) roundf(fabsf(src_w)));
-    const int out_h = PL_DEF(src->new_h, (int) roundf(fabsf(src_h)));
+    const struct src_geometry geo = src_geometry(src);
+    const float src_w = geo.src_w, src_h = geo.src_h;
+    const int out_w = geo.out_w, out_h = geo.out_h;
     if (!out_w || !out_h) {
         SH_FAIL(sh, "Degenerate output size %dx%d", out_w, out_h);
         return false;
@@ -300,6 +315,162 @@ static int polar_taps_gather(uint32_t *taps, pl_filter filter, int bound, bool u
     return n;
 }
 
+/* ---- launch geometry of a polar pass ---------------------------------------------------------- */
+
+#define POLAR_LDS_LIMIT (160 * 1024)    // CDNA4: LDS per CU
+#define POLAR_LUT_BYTES 2048            // the 256 weight pairs in front of the texels
+static const float polar_margin = 1e-5;
+
+// k_polar_band (csrc/hip/k_polar_band.hip): the footprint walked through a ring of source rows.
+// An out_w x out_h tile of output pixels, one per lane, has base texels on at most
+//   span = ceil(out_h / ratio_y) + 1 rows, + 2 of rounding slack (one per side, as k_polar's tile)
+// and the taps of one turn of the walk lie on two rows, so a turn reads span + 1 rows; the one new
+// row of the next turn is staged meanwhile: ring_rows = span + 2. A ring row holds the tile's
+// whole width, ceil(out_w / ratio_x) + 1 + (2 bound - 1) + 2 texels, and that is what costs: the
+// output tile is narrowed until ring and LUT fit `max_lds` (16 x 1 fits at 16x with bound 32 and
+// fp32 texels: 322 x 21 texels = 106 KiB).
+struct polar_band_plan {
+    int out_w, out_h;
+    int ring_rows, ring_w;
+    size_t lds;
+};
+
+static bool polar_band_plan(float ratio_x, float ratio_y, int bound, size_t texel, size_t max_lds,
+                            struct polar_band_plan *out)
+{
+    static const int shapes[][2] = { {32, 8}, {32, 4}, {32, 2}, {32, 1}, {16, 1} };
+    // the reference's own cap (sampling.c:671-674): a row of 2 bound - 1 gathers in a 64-bit mask
+    if (bound < 1 || 2 * bound - 1 >= 64 || !(ratio_x > 0) || !(ratio_y > 0))
+        return false;
+    for (size_t i = 0; i < sizeof(shapes) / sizeof(shapes[0]); i++) {
+        out->out_w = shapes[i][0];
+        out->out_h = shapes[i][1];
+        out->ring_w = (int) ceilf(out->out_w / ratio_x - polar_margin) + 2 * bound + 2;
+        out->ring_rows = (int) ceilf(out->out_h / ratio_y - polar_margin) + 3 + 2;
+        out->lds = POLAR_LUT_BYTES + (size_t) out->ring_w * out->ring_rows * texel;
+        if (out->lds <= max_lds)
+            return true;
+    }
+    return false;
+}
+
+// for tests/test_polar_band_plan.py: out = { out_w, out_h, ring_rows, ring_w, lds }
+PL_API int plh_test_polar_band_plan(float ratio_x, float ratio_y, int bound, int texel, int max_lds,
+                                    int *out);
+int plh_test_polar_band_plan(float ratio_x, float ratio_y, int bound, int texel, int max_lds, int *out)
+{
+    struct polar_band_plan plan;
+    if (!polar_band_plan(ratio_x, ratio_y, bound, texel, max_lds, &plan))
+        return 0;
+    out[0] = plan.out_w;
+    out[1] = plan.out_h;
+    out[2] = plan.ring_rows;
+    out[3] = plan.ring_w;
+    out[4] = (int) plan.lds;
+    return 1;
+}
+
+// Which kernel family stages the source of a polar pass, and how: k_polar and the kernels built
+// on its tile (the whole footprint of a 32 x 8*rows output tile in LDS) wherever that fits, else
+// the band walk. PL_HIP_POLAR_BAND=1 plans the band walk for every pass (the A/B of the two).
+struct polar_geometry {
+    bool band;
+    int rows, tile_w, tile_h;       // !band: k_polar's tile
+    struct polar_band_plan plan;    // band
+    size_t shmem;
+};
+
+static bool polar_geometry(float ratio_x, float ratio_y, int bound, size_t texel,
+                           struct polar_geometry *g)
+{
+    // LDS tile: footprint of a 32 x (8*rows) output tile + filter support
+    // (+2: one texel of rounding slack per side, see k_polar.hip)
+    const int padding = 2 * bound - 1;
+    const size_t max_lds = POLAR_LDS_LIMIT / 2; // keep two workgroups per CU resident
+    g->rows = 4;
+    for (;;) {
+        g->tile_w = (int) ceilf(POLAR_BW / ratio_x - polar_margin) + padding + 1 + 2;
+        g->tile_h = (int) ceilf(POLAR_BH * g->rows / ratio_y - polar_margin) + padding + 1 + 2;
+        if (POLAR_LUT_BYTES + (size_t) g->tile_w * g->tile_h * texel <= max_lds || g->rows == 1)
+            break;
+        g->rows >>= 1;
+    }
+    g->shmem = POLAR_LUT_BYTES + (size_t) g->tile_w * g->tile_h * texel;
+    g->band = g->shmem > POLAR_LDS_LIMIT || plh_switch(PLH_SW_POLAR_BAND) == 1;
+    if (!g->band)
+        return true;
+    if (!polar_band_plan(ratio_x, ratio_y, bound, texel, POLAR_LDS_LIMIT, &g->plan))
+        return false;
+    g->shmem = g->plan.lds;
+    return true;
+}
+
+// What a polar request resolves to before anything is recorded: the sampler object with the
+// (widened) filter generated, and the launch geometry
+struct polar_request {
+    struct sh_sampler_obj *obj;
+    struct pl_filter_config cfg;
+    float ratio_x, ratio_y;
+    int bound;
+    bool fp32_tile;
+    bool over_capacity;     // the radius is beyond the reference's cap: no geometry
+    struct polar_geometry geo;
+};
+
+// Touches `sh` only to fail it (an object of the wrong kind, no memory)
+static bool polar_request(pl_shader sh, const struct pl_sample_src *src,
+                          const struct pl_sample_filter_params *params, bool force_f16_tile,
+                          struct polar_request *rq)
+{
+    memset(rq, 0, sizeof(*rq));
+    const struct src_geometry sg = src_geometry(src);
+    if (!sg.out_w || !sg.out_h)
+        return false;   // (setup_src words it)
+    rq->ratio_x = sg.out_w / fabs(sg.src_w);
+    rq->ratio_y = sg.out_h / fabs(sg.src_h);
+
+    rq->obj = SH_OBJ(sh, params->lut, PL_SHADER_OBJ_SAMPLER, struct sh_sampler_obj, sh_sampler_uninit);
+    if (!rq->obj) {
+        SH_FAIL(sh, "pl_shader_sample_polar requires `params->lut` state");
+        return false;
+    }
+    struct sh_sampler_obj *obj = rq->obj;
+
+    float inv_scale = 1.0 / PL_MIN(rq->ratio_x, rq->ratio_y);
+    inv_scale = PL_MAX(inv_scale, 1.0);
+    if (params->no_widening)
+        inv_scale = 1.0;
+
+    rq->cfg = params->filter;
+    rq->cfg.antiring = PL_DEF(rq->cfg.antiring, params->antiring);
+    rq->cfg.blur = PL_DEF(rq->cfg.blur, 1.0f) * inv_scale;
+    if (!obj->filter || !pl_filter_config_eq(&obj->filter->params.config, &rq->cfg)) {
+        pl_filter_free(&obj->filter);
+        // (its LUT and tap list go with it: sample_polar builds them for the new filter)
+        pl_buf_destroy(SH_GPU(sh), &obj->lut);
+        obj->filter = pl_filter_generate(sh->log, pl_filter_params(
+            .config         = rq->cfg,
+            .lut_entries    = SCALER_LUT_SIZE,
+            .cutoff         = SCALER_LUT_CUTOFF,
+        ));
+        if (!obj->filter) {
+            SH_FAIL(sh, "Failed initializing polar filter!");
+            return false;
+        }
+    }
+
+    rq->bound = ceil(obj->filter->radius);
+    // the LDS texels are f16 only where that is lossless: an rgba16hf source, or the fused
+    // PASS A whose result the reference rounds to an rgba16hf FBO anyway. unorm8/16 and fp32
+    // sources are staged as fp32 (k/255 and k/65535 are not f16 numbers)
+    const pl_fmt sfmt = src->tex->params.format;
+    const bool f16_src = sfmt->type == PL_FMT_FLOAT && sfmt->component_depth[0] == 16;
+    rq->fp32_tile = !force_f16_tile && !f16_src;
+    rq->over_capacity = 2 * rq->bound - 1 >= 64 || rq->bound > 127 ||
+        !polar_geometry(rq->ratio_x, rq->ratio_y, rq->bound, rq->fp32_tile ? 16 : 8, &rq->geo);
+    return true;
+}
+
 static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
                          const struct pl_sample_filter_params *params, bool force_f16_tile);
 
@@ -322,40 +493,17 @@ static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
         return false;
 
     pl_gpu gpu = SH_GPU(sh);
-    struct sh_sampler_obj *obj = SH_OBJ(sh, params->lut, PL_SHADER_OBJ_SAMPLER,
-                                        struct sh_sampler_obj, sh_sampler_uninit);
-    if (!obj) {
-        SH_FAIL(sh, "pl_shader_sample_polar requires `params->lut` state");
+    struct polar_request rq;
+    if (!polar_request(sh, src, params, force_f16_tile, &rq))
         return false;
-    }
-
-    float inv_scale = 1.0 / PL_MIN(info.ratio_x, info.ratio_y);
-    inv_scale = PL_MAX(inv_scale, 1.0);
-    if (params->no_widening)
-        inv_scale = 1.0;
-
-    struct pl_filter_config cfg = params->filter;
-    cfg.antiring = PL_DEF(cfg.antiring, params->antiring);
-    cfg.blur = PL_DEF(cfg.blur, 1.0f) * inv_scale;
-    const bool update = !obj->filter || !pl_filter_config_eq(&obj->filter->params.config, &cfg);
-    if (update) {
-        pl_filter_free(&obj->filter);
-        obj->filter = pl_filter_generate(sh->log, pl_filter_params(
-            .config         = cfg,
-            .lut_entries    = SCALER_LUT_SIZE,
-            .cutoff         = SCALER_LUT_CUTOFF,
-        ));
-        if (!obj->filter) {
-            SH_FAIL(sh, "Failed initializing polar filter!");
-            return false;
-        }
-    }
+    struct sh_sampler_obj *obj = rq.obj;
+    const struct pl_filter_config cfg = rq.cfg;
 
     describe_filter(sh, &cfg, "polar", info.ratio_x, info.ratio_y);
     pl_filter filter = obj->filter;
     const bool use_ar = cfg.antiring > 0;
-    const int bound = ceil(filter->radius);
-    if (2 * bound - 1 >= 64 || bound > 127) {
+    const int bound = rq.bound;
+    if (rq.over_capacity) {
         SH_FAIL(sh, "Polar radius %f exceeds implementation capacity!", filter->radius);
         return false;
     }
@@ -366,7 +514,7 @@ static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
     const struct pl_glsl_version glsl = sh_glsl(sh);
     const bool gather_order = params->no_compute || !(filter->radius < 6.0);
 
-    if (update || !obj->lut || !obj->polar.taps || obj->taps_gather != gather_order) {
+    if (!obj->lut || !obj->polar.taps || obj->taps_gather != gather_order) {
         // weight LUT as {L[i], L[min(i+1, 255)]} pairs: one ds_read_b64 per tap
         float pairs[2 * SCALER_LUT_SIZE];
         for (int i = 0; i < SCALER_LUT_SIZE; i++) {
@@ -397,33 +545,14 @@ static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
         }
     }
 
-    // LDS tile: footprint of a 32 x (8*rows) output tile + filter support
-    // (+2: one texel of rounding slack per side, see k_polar.hip)
-    const int padding = 2 * bound - 1;
-    const float margin = 1e-5;
-    // the LDS tile holds f16 texels only where that is lossless: an rgba16hf source, or the fused
-    // PASS A whose result the reference rounds to an rgba16hf FBO anyway. unorm8/16 and fp32
-    // sources are staged as fp32 (k/255 and k/65535 are not f16 numbers)
-    const pl_fmt sfmt = src->tex->params.format;
-    const bool f16_src = sfmt->type == PL_FMT_FLOAT && sfmt->component_depth[0] == 16;
-    const bool fp32_tile = !force_f16_tile && !f16_src;
-    const size_t texel = fp32_tile ? 16 : 8;
-    const size_t max_lds = 160 * 1024 / 2; // keep two workgroups per CU resident
-    int rows = 4, tile_w, tile_h;
-    for (;;) {
-        tile_w = (int) ceilf(POLAR_BW / info.ratio_x - margin) + padding + 1 + 2;
-        tile_h = (int) ceilf(POLAR_BH * rows / info.ratio_y - margin) + padding + 1 + 2;
-        if (2048 + (size_t) tile_w * tile_h * texel <= max_lds || rows == 1)
-            break;
-        rows >>= 1;
-    }
-    const size_t shmem = 2048 + (size_t) tile_w * tile_h * texel;
-    if (shmem > 160 * 1024) {
-        SH_FAIL(sh, "Polar filter footprint (%dx%d texels) does not fit in LDS", tile_w, tile_h);
-        return false;
-    }
-    sh_try_compute(sh, POLAR_BW, POLAR_BH * rows, false, 0);
-    sh->shmem = shmem;
+    // k_polar's tile, or the band walk where that is above the LDS (polar_geometry)
+    const struct polar_geometry *geo = &rq.geo;
+    const bool fp32_tile = rq.fp32_tile;
+    if (geo->band)
+        sh_try_compute(sh, geo->plan.out_w, geo->plan.out_h, false, 0);
+    else
+        sh_try_compute(sh, POLAR_BW, POLAR_BH * geo->rows, false, 0);
+    sh->shmem = geo->shmem;
 
     struct plh_sampler_args *s = &sh->pass.s;
     s->type = PLH_SAMPLE_POLAR;
@@ -435,19 +564,34 @@ static bool sample_polar(pl_shader sh, const struct pl_sample_src *src,
     s->rcp_radius = 1.0f / filter->radius;
     s->radius_zero = filter->radius_zero;
     s->antiring = cfg.antiring;
-    s->tile_w = tile_w;
-    s->tile_h = tile_h;
-    s->tile_rows = rows;
+    s->tile_w = geo->band ? geo->plan.ring_w : geo->tile_w;
+    s->tile_h = geo->band ? geo->plan.ring_rows : geo->tile_h;
+    s->tile_rows = geo->band ? 1 : geo->rows;
     s->tile_fp32 = fp32_tile;
+    s->band_rows = geo->band ? geo->plan.ring_rows : 0;
+    s->band_w = geo->plan.ring_w;
+    s->band_out_w = geo->plan.out_w;
+    s->band_out_h = geo->plan.out_h;
     s->pp = NULL;
-    sh->polar_obj = use_ar ? NULL : &obj->polar;   // anti-ringing needs per-pixel d, see k_polar
+    // (anti-ringing needs per-pixel d, see k_polar; the band walk has no tables either)
+    sh->polar_obj = use_ar || geo->band ? NULL : &obj->polar;
     sh_hold(sh, *params->lut);
 
+    if (geo->band) {
+        sh_listf(sh, "sample_polar(filter=%s, radius=%f, radius_zero=%f, taps=%d (%s order), "
+                 "band: ring=%dx%d %s, %zu B of LDS, %dx%d outputs per workgroup, antiring=%g, "
+                 "scale=%g, mask=0x%x)\n",
+                 PL_DEF(cfg.name, "custom"), filter->radius, filter->radius_zero, obj->num_taps,
+                 gather_order ? "gather" : "compute", geo->plan.ring_w, geo->plan.ring_rows,
+                 fp32_tile ? "f32" : "f16", geo->shmem, geo->plan.out_w, geo->plan.out_h,
+                 cfg.antiring, info.scale, info.comp_mask);
+        return true;
+    }
     sh_listf(sh, "sample_polar(filter=%s, radius=%f, radius_zero=%f, taps=%d (%s order), "
              "tile=%dx%d %s, rows=%d, antiring=%g, scale=%g, mask=0x%x)\n",
              PL_DEF(cfg.name, "custom"), filter->radius, filter->radius_zero, obj->num_taps,
-             gather_order ? "gather" : "compute", tile_w, tile_h, fp32_tile ? "f32" : "f16",
-             rows, cfg.antiring, info.scale, info.comp_mask);
+             gather_order ? "gather" : "compute", geo->tile_w, geo->tile_h, fp32_tile ? "f32" : "f16",
+             geo->rows, cfg.antiring, info.scale, info.comp_mask);
     return true;
 }
 
@@ -542,6 +686,11 @@ bool plh_shader_sample_polar_fused(pl_shader sh, const pl_shader pre,
     struct pl_sample_src fsrc = *src;
     fsrc.tex = tex;
     fsrc.address_mode = pp->s.address_mode;
+    // the band walk stages a source texel more than once and takes no pre-ops: such a request
+    // (and one beyond the radius cap, which pl_shader_sample_polar words) reads an intermediate
+    struct polar_request rq;
+    if (!polar_request(sh, &fsrc, params, true, &rq) || rq.over_capacity || rq.geo.band)
+        return false;
     if (!sample_polar(sh, &fsrc, params, true))
         return false;
 
